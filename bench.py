@@ -5,11 +5,18 @@ Workload (BASELINE.json metric config — the 8-run merge the headline metric
 is quoted on): config 3 = 8 runs x ~1 GiB, 32 B keys / 1 KiB values, 50% key
 overlap, 5% tombstones, synthetic seeded runs (no network). A "step" = one
 full compaction of the 8-run set with inputs already resident in HBM
-(outputs land in HBM). The default line also carries `end_to_end`: the
-PCIe-inclusive streamed-pinned-ingest rate measured beside the resident
-metric (never as `value` — SURVEY.md §8d), plus `cpu_baseline` (the C
-oracle restatement on the box's host cores). Other BASELINE shapes via
+(outputs land in HBM). A plain run sets up, warms up, times the steps and
+prints the result line (per-stage `kernel_ms` and the roofline objects come
+from the timed steps' own HIP events, at no extra cost). With `--full` the
+line also carries `end_to_end`: the PCIe-inclusive streamed-pinned-ingest
+rate measured beside the resident metric (never as `value` — SURVEY.md
+§8d), plus `cpu_baseline` (the C oracle restatement on the host cores);
+both are null without it. Other BASELINE shapes via
 --workload cfg2/cfg4/cfg5.
+
+`--dump-outputs DIR` writes what the last timed step computed (each job's
+compacted data/index files, fetched from HBM) as DIR/<name>.npy: whole-file
+block checksums plus a fixed seeded sample of entries (see dump_outputs).
 
 Multi-GPU: the path shards as INDEPENDENT jobs — one
 compaction job per GPU (weak scaling), with the only collective an RCCL
@@ -17,6 +24,7 @@ all-gather of per-rank emitted byte counts (8 x u64-scale) per step, per the
 north star.
 
 Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--scale S]
+                        [--full] [--dump-outputs DIR]
 For N>1 the driver launches via torch.distributed.run (one rank per GPU);
 rank/device from RANK/LOCAL_RANK/WORLD_SIZE.
 """
@@ -119,6 +127,76 @@ def aux_record_bytes(key_size: int) -> int:
     return 16 if key_size <= 20 else (48 if key_size <= 32 else 64)
 
 
+DUMP_SEED = 0xD0C5
+DUMP_SAMPLE_ENTRIES = 4096      # per run of the benchmark, over all jobs
+DUMP_SAMPLE_BYTES = 10 << 20    # sampled entry bytes (x4 once float32)
+DUMP_DATA_BLOCK = 1 << 20
+DUMP_INDEX_BLOCK = 1 << 16
+
+
+def _block_word_sums(buf, block: int):
+    """Per-block checksum of a byte array: the sum of its little-endian
+    u32 words (zero-padded tail). block/4 words of < 2^32 sum to < 2^53,
+    so every figure is exact in float64."""
+    import numpy as np
+
+    a = np.frombuffer(buf, dtype=np.uint8)
+    full = (a.size // block) * block
+    sums = a[:full].view("<u4").reshape(-1, block // 4).sum(
+        axis=1, dtype=np.uint64)
+    if full < a.size:
+        tail = np.zeros(block, dtype=np.uint8)
+        tail[: a.size - full] = a[full:]
+        sums = np.append(sums, tail.view("<u4").sum(dtype=np.uint64))
+    return sums.astype(np.float64)
+
+
+def dump_outputs(out_dir: str, results):
+    """Write the compacted output of every job as DIR/<name>.npy.
+
+    results: [(data_bytes, index_bytes, n_entries), ...], one per job, as
+    Job.fetch() returns them. The outputs are GiB-sized byte files, so per
+    job j this stores (float64 unless noted, every value exact):
+      job{j}_summary          [data bytes, index bytes, entries]
+      job{j}_data_blocks      u32-word sum of each 1 MiB block of the data
+      job{j}_index_blocks     same per 64 KiB block of the index
+      job{j}_sample_ids       fixed seeded sample of entry numbers
+      job{j}_sample_index     their (offset, key_size, full_size) records
+      job{j}_sample_data      their entry bytes, concatenated (float32)
+    The sample depends only on DUMP_SEED and the entry count and sizes, so
+    two builds that compute the same output write identical files."""
+    import numpy as np
+
+    from dbeel_amd.format import INDEX_DTYPE
+
+    os.makedirs(out_dir, exist_ok=True)
+    n_jobs = max(1, len(results))
+    for j, (data, index, n) in enumerate(results):
+        def save(name, arr):
+            np.save(os.path.join(out_dir, f"job{j}_{name}.npy"), arr)
+
+        save("summary", np.array([len(data), len(index), n],
+                                 dtype=np.float64))
+        save("data_blocks", _block_word_sums(data, DUMP_DATA_BLOCK))
+        save("index_blocks", _block_word_sums(index, DUMP_INDEX_BLOCK))
+        recs = np.frombuffer(index, dtype=INDEX_DTYPE)
+        rng = np.random.default_rng(DUMP_SEED + j)
+        want = min(recs.size, max(1, DUMP_SAMPLE_ENTRIES // n_jobs))
+        ids = (rng.choice(recs.size, size=want, replace=False) if want
+               else np.zeros(0, dtype=np.int64))
+        fits = np.cumsum(recs["full_size"][ids].astype(np.int64))
+        ids = np.sort(ids[fits <= DUMP_SAMPLE_BYTES // n_jobs])
+        d = np.frombuffer(data, dtype=np.uint8)
+        parts = [d[int(o): int(o) + int(f)]
+                 for o, f in zip(recs["offset"][ids], recs["full_size"][ids])]
+        save("sample_ids", ids.astype(np.float64))
+        save("sample_index", np.stack(
+            [recs[f][ids].astype(np.float64)
+             for f in ("offset", "key_size", "full_size")], axis=1))
+        save("sample_data", np.concatenate(parts).astype(np.float32)
+             if parts else np.zeros(0, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -132,15 +210,26 @@ def main():
                          "cfg3 = 8-run x 1 GiB metric config; cfg4 = 8 "
                          "independent 4-run x 256 MiB jobs per GPU; cfg5 = "
                          "16-run var-length msgpack keys + 4 KiB values")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the end-to-end "
+                         "streamed-ingest rate and the CPU baseline "
+                         "(runs of their own; both null without it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as "
+                         "DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--skip-streamed", action="store_true",
-                    help="skip the end-to-end streamed-ingest measurement")
+                    help="with --full: skip the end-to-end streamed-ingest "
+                         "measurement")
     ap.add_argument("--keep-tombstones", action="store_true")
     ap.add_argument("--cpu-baseline-scale", type=float, default=1.0,
                     help="fraction of the workload timed on the host "
                          "(default: the whole workload, one single-threaded "
                          "oracle job per core)")
-    ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument("--skip-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
 
@@ -242,6 +331,16 @@ def main():
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e.item())
 
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives: each job's output
+        # files, fetched from HBM as the last timed step left them
+        if isinstance(jobs[0], dbeel_amd.engine.BatchJob):
+            fetched = [jobs[0].fetch_job(j) for j in range(jobs[0].n_jobs)]
+        else:
+            fetched = [j.fetch() for j in jobs]
+        dump_outputs(args.dump_outputs, fetched)
+        del fetched
+
     ms_per_step = elapsed * 1000.0 / args.steps
     total_input = input_bytes * n_gpus
     value = (total_input / 1e6) / (elapsed / args.steps)  # MB/s, whole job
@@ -319,7 +418,7 @@ def main():
     # beside the resident metric ("end-to-end MB/s incl.
     # PCIe streaming is also reported"); never `value`.
     end_to_end = None
-    if (rank == 0 and n_gpus == 1 and not args.skip_streamed
+    if (args.full and rank == 0 and n_gpus == 1 and not args.skip_streamed
             and len(jobs) == 1):
         from dbeel_amd.engine import pin_host, unpin_host
 
@@ -361,7 +460,8 @@ def main():
                         pass
 
     cpu_baseline = None
-    if rank == 0 and n_gpus == 1 and not args.skip_cpu_baseline:
+    if (args.full and rank == 0 and n_gpus == 1
+            and not args.skip_cpu_baseline):
         import oracle
 
         bs = args.cpu_baseline_scale * args.scale
