@@ -11,10 +11,12 @@ from .engine import (  # noqa: F401
     BatchJob,
     DbeelGpuError,
     Job,
+    Reader,
     compact,
     compact_sliced,
     encode_run,
     lookup,
+    lookup_raw,
     pin_host,
     scan,
     unpin_host,
@@ -23,4 +25,5 @@ from .engine import (  # noqa: F401
 __all__ = [
     "compact", "compact_sliced", "scan", "lookup", "encode_run",
     "Job", "BatchJob", "pin_host", "unpin_host", "DbeelGpuError", "format",
+    "Reader", "lookup_raw",
 ]

@@ -42,6 +42,10 @@
  *                  ranges + key bounds — lsm_tree.rs:141-282,
  *                  tasks/migration.rs:54-60).
  *   k_encode_*   : the memtable-flush run encoder (lsm_tree.rs:925-946).
+ *   k_reader_*   : the resident table reader (LSMTree::get over the
+ *                  sstables, lsm_tree.rs:674-723): open-time validation
+ *                  + prefix array, batched search with the on-device
+ *                  bloom prefilter, value gather.
  *   host side    : resident jobs, batched independent jobs (one launch
  *                  set, per-job output slicing), streamed pinned ingest
  *                  with copy/compute overlap, sliced compaction for
@@ -78,6 +82,13 @@ static void set_err(const char* fmt, ...) {
 }
 
 extern "C" const char* dbeel_gpu_last_error(void) { return g_err; }
+
+/* Library-internal: lets the file-level layer (dbeel_lsm.cpp, linked into
+ * the same .so) report through dbeel_gpu_last_error. Not exported. */
+extern "C" __attribute__((visibility("hidden"))) void dbeel_set_last_error(
+    const char* msg) {
+    set_err("%s", msg);
+}
 
 #define HIP_CHECK(call)                                                     \
     do {                                                                    \
@@ -2388,6 +2399,602 @@ extern "C" int dbeel_gpu_lookup(const dbeel_run_view* runs, size_t n_runs,
         return DBEEL_ERR_HIP;
     }
     return DBEEL_OK;
+}
+
+/* ------------------------------------------------------------------ */
+/* Resident table reader                                              */
+/*                                                                    */
+/* dbeel_gpu_lookup above answers one batch by building a whole       */
+/* compaction job. The reader keeps what a read needs resident — the  */
+/* padded run slab, one dense big-endian 8-byte key prefix per entry  */
+/* and the runs' "DBLM" filter bitmaps — and answers any number of    */
+/* batches against it:                                                */
+/*   k_reader_prepare : open-time pass; k_prepare's checks (bounds,   */
+/*                      bincode field cross-check, monotone offsets)  */
+/*                      plus strict key order inside each run, and    */
+/*                      the prefix array. No aux records.             */
+/*   k_reader_search  : thread per query; runs newest-index-first     */
+/*                      (lsm_tree.rs:692-696): filter check with      */
+/*                      early out, lower bound over the run's dense   */
+/*                      prefix slice (8 keys per 64-B line, top       */
+/*                      levels cache-resident), then the equal-prefix */
+/*                      range is resolved by binary search with full  */
+/*                      key compares on the blob.                     */
+/*   rocPRIM scan     : value_len -> exclusive value offsets.         */
+/*   k_reader_gather  : wave per hit, 8-B chunks, exact-length reads. */
+/* ------------------------------------------------------------------ */
+
+struct ReaderBloom {
+    const uint8_t* bits; /* device bitmap; NULL = run has no filter */
+    uint64_t n_bits;
+    uint64_t seed;
+    uint32_t k;
+    uint32_t rsv;
+};
+
+/* stats slots of dbeel_get_stats, in order */
+enum { RS_PROBES, RS_SKIPS, RS_SEARCHES, RS_HITS, RS_TOMBS, RS_N };
+
+#define READER_BLOCK 256
+
+__global__ void k_reader_prepare(RunsDesc R, uint64_t* pfx, uint32_t* err) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         g < R.total; g += stride) {
+        int r = 0;
+        while (r + 1 < R.n_runs && g >= R.entry_base[r + 1]) r++;
+        uint64_t i = g - R.entry_base[r];
+        EView e;
+        /* offset checked on its own first: off + full_size must not wrap */
+        if (ld_u64(R.index[r] + i * 16) > R.data_len[r] ||
+            !load_entry(R, r, i, e)) {
+            atomicOr(err, DERR_CORRUPT);
+            pfx[g] = 0;
+            continue;
+        }
+        pfx[g] = key_prefix(e.key, e.klen);
+        /* bincode field cross-check */
+        if (ld_u64(e.raw) != e.klen ||
+            ld_u64(e.raw + 8 + e.klen) != (uint64_t)e.full_size - 32 - e.klen)
+            atomicOr(err, DERR_CORRUPT);
+        if (i + 1 < R.count[r]) {
+            uint64_t noff = ld_u64(R.index[r] + (i + 1) * 16);
+            if (e.off + e.full_size > noff) atomicOr(err, DERR_CORRUPT);
+            /* the search depends on strictly ascending keys
+             * (flush invariant, lsm_tree.rs:925-946); an invalid
+             * successor is flagged by its own thread */
+            EView nx;
+            if (noff <= R.data_len[r] && load_entry(R, r, i + 1, nx) &&
+                cmp_keys(e.key, e.klen, nx.key, nx.klen) >= 0)
+                atomicOr(err, DERR_UNSORTED);
+        }
+    }
+}
+
+__global__ __launch_bounds__(READER_BLOCK) void k_reader_search(
+    RunsDesc R, const uint64_t* pfx, const ReaderBloom* blooms,
+    const uint8_t* keys, const uint64_t* key_off, uint64_t n_keys,
+    dbeel_lookup_hit* out, unsigned long long* stats) {
+    __shared__ unsigned long long s_stats[RS_N];
+    if (threadIdx.x < RS_N) s_stats[threadIdx.x] = 0;
+    __syncthreads();
+    unsigned long long c[RS_N] = {};
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         q < n_keys; q += stride) {
+        const uint8_t* key = keys + key_off[q];
+        uint64_t klen = key_off[q + 1] - key_off[q];
+        const uint64_t qp = key_prefix(key, klen);
+        /* hash pair of the filter seed last seen: filters written by
+         * this engine share one seed, so it is computed once per query,
+         * and only if a filtered run is reached */
+        bool have_hash = false;
+        uint64_t hseed = 0, h1 = 0, h2 = 0;
+        int best_run = -1;
+        uint64_t best_off = 0, best_vlen = 0;
+        for (int r = R.n_runs - 1; r >= 0; r--) {
+            const ReaderBloom B = blooms[r];
+            if (B.bits) {
+                c[RS_PROBES]++;
+                if (!have_hash || hseed != B.seed) {
+                    hseed = B.seed;
+                    h1 = d_fnv1a64(key, klen, hseed);
+                    h2 = d_fnv1a64(key, klen,
+                                   hseed ^ 0x9e3779b97f4a7c15ull) | 1;
+                    have_hash = true;
+                }
+                bool maybe = true;
+                for (uint32_t j = 0; j < B.k; j++) {
+                    uint64_t bit = (h1 + j * h2) % B.n_bits;
+                    if (!(B.bits[bit >> 3] & (1u << (bit & 7)))) {
+                        maybe = false;
+                        break;
+                    }
+                }
+                if (!maybe) {
+                    c[RS_SKIPS]++;
+                    continue;
+                }
+            }
+            c[RS_SEARCHES]++;
+            const uint64_t* P = pfx + R.entry_base[r];
+            const uint64_t n = R.count[r];
+            uint64_t lo = 0, hi = n;
+            while (lo < hi) {
+                uint64_t mid = (lo + hi) >> 1;
+                if (P[mid] < qp)
+                    lo = mid + 1;
+                else
+                    hi = mid;
+            }
+            if (lo >= n || P[lo] != qp) continue;
+            /* [lo, end) = entries sharing the query's prefix. Usually
+             * one entry; otherwise its end is found by a second
+             * bisection, never a walk */
+            uint64_t end = lo + 1;
+            if (end < n && P[end] == qp) {
+                uint64_t a = end + 1, b = n;
+                while (a < b) {
+                    uint64_t mid = (a + b) >> 1;
+                    if (P[mid] <= qp)
+                        a = mid + 1;
+                    else
+                        b = mid;
+                }
+                end = a;
+            }
+            /* equal prefixes are not equal keys (zero padding, length,
+             * bytes past 8): the full compare on the blob decides. Keys
+             * are unique inside a run, so a zero compare is the match */
+            bool found = false;
+            EView m;
+            while (lo < end) {
+                uint64_t mid = (lo + end) >> 1;
+                if (!load_entry(R, r, mid, m)) { /* validated at open */
+                    end = mid;
+                    continue;
+                }
+                int cmp = cmp_keys(m.key, m.klen, key, klen);
+                if (cmp == 0) {
+                    found = true;
+                    break;
+                }
+                if (cmp < 0)
+                    lo = mid + 1;
+                else
+                    end = mid;
+            }
+            if (!found) continue;
+            best_run = r;
+            best_off = m.off + 16 + m.klen; /* value bytes start */
+            best_vlen = (uint64_t)m.full_size - 32 - m.klen;
+            break;
+        }
+        if (best_run >= 0) {
+            c[RS_HITS]++;
+            if (best_vlen == 0) c[RS_TOMBS]++;
+        }
+        out[q].run = best_run;
+        out[q].is_tombstone = (best_run >= 0 && best_vlen == 0) ? 1 : 0;
+        out[q].value_offset = best_off;
+        out[q].value_len = best_vlen;
+    }
+    #pragma unroll
+    for (int s = 0; s < RS_N; s++)
+        if (c[s]) atomicAdd(&s_stats[s], c[s]);
+    __syncthreads();
+    if (threadIdx.x < RS_N && s_stats[threadIdx.x])
+        atomicAdd(&stats[threadIdx.x], s_stats[threadIdx.x]);
+}
+
+struct HitValueLen {
+    __device__ uint64_t operator()(const dbeel_lookup_hit& h) const {
+        return h.value_len;
+    }
+};
+
+/* One wave per query moves its value in 8-B chunks (byte tail by lane 0),
+ * reading exactly value_len bytes — k_copy's staged span assumes >= 32-B
+ * segments and cannot take 0/1-byte values. */
+__global__ void k_reader_gather(RunsDesc R, const dbeel_lookup_hit* hits,
+                                const uint64_t* val_off, uint64_t n_keys,
+                                uint8_t* values) {
+    uint32_t lane = threadIdx.x & 63;
+    uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    for (uint64_t q = wave; q < n_keys; q += n_waves) {
+        const dbeel_lookup_hit h = hits[q];
+        if (h.run < 0 || h.value_len == 0) continue;
+        wave_copy_bytes(values + val_off[q], R.data[h.run] + h.value_offset,
+                        h.value_len, lane);
+    }
+}
+
+struct dbeel_gpu_reader {
+    int device = -1;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[7] = {};
+    RunsDesc desc{};
+    uint8_t* d_slab = nullptr;      /* all run data+index, +-16 B padded */
+    uint64_t* d_pfx = nullptr;      /* dense big-endian key prefixes     */
+    uint8_t* d_bitmaps = nullptr;   /* filter bitmaps, 8-B aligned each  */
+    ReaderBloom* d_blooms = nullptr; /* n_runs descriptors               */
+    uint64_t table_bytes = 0;
+    /* per-batch scratch, grown on demand and reused */
+    uint8_t* d_keys = nullptr;
+    uint64_t keys_cap = 0;
+    uint8_t* d_batch = nullptr; /* key offsets | value offsets | hits */
+    uint64_t batch_cap = 0;
+    void* d_scantmp = nullptr;
+    uint64_t scantmp_cap = 0;
+    uint8_t* d_values = nullptr;
+    uint64_t values_cap = 0;
+    unsigned long long* d_stats = nullptr;
+};
+
+static hipError_t reader_reserve(void** p, uint64_t* cap, uint64_t need) {
+    if (need <= *cap) return hipSuccess;
+    (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    uint64_t want = need + need / 4;
+    hipError_t e = hipMalloc(p, want);
+    if (e == hipSuccess) *cap = want;
+    return e;
+}
+
+extern "C" void dbeel_gpu_reader_close(dbeel_gpu_reader* rd) {
+    if (!rd) return;
+    if (rd->device >= 0) (void)hipSetDevice(rd->device);
+    if (rd->stream) (void)hipStreamSynchronize(rd->stream);
+    (void)hipFree(rd->d_slab);
+    (void)hipFree(rd->d_pfx);
+    (void)hipFree(rd->d_bitmaps);
+    (void)hipFree(rd->d_blooms);
+    (void)hipFree(rd->d_keys);
+    (void)hipFree(rd->d_batch);
+    (void)hipFree(rd->d_scantmp);
+    (void)hipFree(rd->d_values);
+    (void)hipFree(rd->d_stats);
+    for (int i = 0; i < 7; i++)
+        if (rd->ev[i]) (void)hipEventDestroy(rd->ev[i]);
+    if (rd->stream) (void)hipStreamDestroy(rd->stream);
+    delete rd;
+}
+
+extern "C" uint64_t dbeel_gpu_reader_table_bytes(const dbeel_gpu_reader* rd) {
+    return rd ? rd->table_bytes : 0;
+}
+
+/* "DBLM" header (include/dbeel_lsm.h): magic | ver | k | pad | n_bits |
+ * seed, then the bitmap. Same acceptance rules as dbeel_bloom_contains. */
+static int parse_bloom(const dbeel_bloom_view& v, size_t r,
+                       ReaderBloom* out) {
+    uint32_t ver, k;
+    uint64_t n_bits, seed;
+    if (v.len < 32 || memcmp(v.bytes, "DBLM", 4) != 0) {
+        set_err("run %zu: filter is not a DBLM file", r);
+        return DBEEL_ERR_CORRUPT;
+    }
+    memcpy(&ver, v.bytes + 4, 4);
+    memcpy(&k, v.bytes + 8, 4);
+    memcpy(&n_bits, v.bytes + 16, 8);
+    memcpy(&seed, v.bytes + 24, 8);
+    if (ver != 1) {
+        set_err("run %zu: filter version %u unsupported", r, ver);
+        return DBEEL_ERR_CORRUPT;
+    }
+    if (n_bits == 0) { /* the probe's modulus */
+        set_err("run %zu: filter header declares zero bits", r);
+        return DBEEL_ERR_CORRUPT;
+    }
+    if (n_bits > (uint64_t)(v.len - 32) * 8) {
+        set_err("run %zu: filter of %zu bytes is shorter than its header's "
+                "%llu bits", r, v.len, (unsigned long long)n_bits);
+        return DBEEL_ERR_CORRUPT;
+    }
+    out->bits = nullptr;
+    out->n_bits = n_bits;
+    out->seed = seed;
+    out->k = k;
+    out->rsv = 0;
+    return DBEEL_OK;
+}
+
+extern "C" int dbeel_gpu_reader_open(const dbeel_run_view* runs,
+                                     const dbeel_bloom_view* blooms,
+                                     size_t n_runs, int device,
+                                     dbeel_gpu_reader** out_reader) {
+    g_err[0] = 0;
+    if (!out_reader) {
+        set_err("reader_open: out is null");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    *out_reader = nullptr;
+    int rc = validate_runs(runs, n_runs);
+    if (rc) return rc;
+    if (device < 0) {
+        set_err("device must be >= 0 (no CPU fallback)");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    ReaderBloom hb[MAX_RUNS];
+    uint64_t bm_off[MAX_RUNS];
+    uint64_t bitmap_bytes = 0;
+    memset(hb, 0, sizeof hb);
+    for (size_t r = 0; r < n_runs; r++) {
+        bm_off[r] = bitmap_bytes;
+        if (!blooms || !blooms[r].bytes) continue;
+        rc = parse_bloom(blooms[r], r, &hb[r]);
+        if (rc) return rc;
+        bitmap_bytes += ((hb[r].n_bits + 7) / 8 + 7) & ~7ull;
+    }
+
+    int ndev = 0;
+    hipError_t de = hipGetDeviceCount(&ndev);
+    if (de != hipSuccess || device >= ndev) {
+        set_err("no usable HIP device %d (count=%d, %s)", device, ndev,
+                hipGetErrorString(de));
+        return DBEEL_ERR_NO_GPU;
+    }
+    HIP_CHECK(hipSetDevice(device));
+
+    dbeel_gpu_reader* rd = new (std::nothrow) dbeel_gpu_reader();
+    if (!rd) return DBEEL_ERR_OOM;
+    rd->device = device;
+
+#define RD_CHECK(call)                                                      \
+    do {                                                                    \
+        hipError_t _e = (call);                                             \
+        if (_e != hipSuccess) {                                             \
+            set_err("%s failed: %s", #call, hipGetErrorString(_e));         \
+            dbeel_gpu_reader_close(rd);                                     \
+            return (_e == hipErrorOutOfMemory) ? DBEEL_ERR_OOM              \
+                                               : DBEEL_ERR_HIP;             \
+        }                                                                   \
+    } while (0)
+
+    uint64_t input_bytes = 0, total = 0;
+    for (size_t r = 0; r < n_runs; r++) {
+        input_bytes += runs[r].data_len + runs[r].index_len;
+        total += runs[r].index_len / 16;
+    }
+    const uint64_t slab_bytes = (input_bytes ? input_bytes : 16) + 32;
+    const uint64_t pfx_bytes = (total ? total : 1) * sizeof(uint64_t);
+    uint32_t* d_err = nullptr;
+    uint32_t err = 0;
+
+    RD_CHECK(hipStreamCreate(&rd->stream));
+    for (int i = 0; i < 7; i++) RD_CHECK(hipEventCreate(&rd->ev[i]));
+    /* same +-16 B padding as a job's input slab */
+    RD_CHECK(hipMalloc(&rd->d_slab, slab_bytes));
+    RD_CHECK(hipMalloc(&rd->d_pfx, pfx_bytes));
+    RD_CHECK(hipMalloc(&rd->d_bitmaps, bitmap_bytes ? bitmap_bytes : 8));
+    RD_CHECK(hipMalloc(&rd->d_blooms, MAX_RUNS * sizeof(ReaderBloom)));
+    RD_CHECK(hipMalloc(&rd->d_stats, (RS_N + 1) * sizeof(uint64_t)));
+    rd->table_bytes = slab_bytes + pfx_bytes + bitmap_bytes;
+    d_err = (uint32_t*)(rd->d_stats + RS_N);
+
+    {
+        uint8_t* p = rd->d_slab + 16;
+        RunsDesc& D = rd->desc;
+        memset(&D, 0, sizeof D);
+        D.n_runs = (int)n_runs;
+        D.total = total;
+        uint64_t base = 0;
+        for (size_t r = 0; r < n_runs; r++) {
+            D.data[r] = p;
+            D.data_len[r] = runs[r].data_len;
+            if (runs[r].data_len) {
+                RD_CHECK(hipMemcpyAsync(p, runs[r].data, runs[r].data_len,
+                                        hipMemcpyHostToDevice, rd->stream));
+                p += runs[r].data_len;
+            }
+            D.index[r] = p;
+            D.count[r] = runs[r].index_len / 16;
+            if (runs[r].index_len) {
+                RD_CHECK(hipMemcpyAsync(p, runs[r].index, runs[r].index_len,
+                                        hipMemcpyHostToDevice, rd->stream));
+                p += runs[r].index_len;
+            }
+            D.entry_base[r] = base;
+            base += D.count[r];
+            if (blooms && blooms[r].bytes) {
+                uint8_t* b = rd->d_bitmaps + bm_off[r];
+                RD_CHECK(hipMemcpyAsync(b, blooms[r].bytes + 32,
+                                        (hb[r].n_bits + 7) / 8,
+                                        hipMemcpyHostToDevice, rd->stream));
+                hb[r].bits = b;
+            }
+        }
+    }
+    RD_CHECK(hipMemcpyAsync(rd->d_blooms, hb, sizeof hb,
+                            hipMemcpyHostToDevice, rd->stream));
+    RD_CHECK(hipMemsetAsync(d_err, 0, sizeof(uint64_t), rd->stream));
+    if (total)
+        hipLaunchKernelGGL(k_reader_prepare, dim3(pick_grid(total, 256)),
+                           dim3(256), 0, rd->stream, rd->desc, rd->d_pfx,
+                           d_err);
+    RD_CHECK(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost,
+                            rd->stream));
+    /* hb and the caller's buffers are read by the async copies above */
+    RD_CHECK(hipStreamSynchronize(rd->stream));
+    RD_CHECK(hipGetLastError());
+#undef RD_CHECK
+    if (err) {
+        set_err(err & DERR_CORRUPT
+                    ? "corrupt input run (entry bounds/fields)"
+                    : "input run is not strictly ascending by key");
+        dbeel_gpu_reader_close(rd);
+        return DBEEL_ERR_CORRUPT;
+    }
+    *out_reader = rd;
+    return DBEEL_OK;
+}
+
+extern "C" void dbeel_gpu_get_result_free(dbeel_get_result* r) {
+    if (!r) return;
+    free(r->hits);
+    free(r->value_offsets);
+    free(r->values);
+    memset(r, 0, sizeof *r);
+}
+
+extern "C" int dbeel_gpu_reader_get(dbeel_gpu_reader* rd,
+                                    const uint8_t* keys,
+                                    const uint64_t* key_offsets,
+                                    uint64_t n_keys, dbeel_get_result* out,
+                                    dbeel_get_stats* stats) {
+    g_err[0] = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (!rd || !out || (n_keys && (!keys || !key_offsets))) {
+        set_err("reader_get: null argument");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    memset(out, 0, sizeof *out);
+    if (n_keys >= (1ull << 32)) {
+        set_err("reader_get: 2^32 or more keys in one batch");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    for (uint64_t i = 0; i < n_keys; i++)
+        if (key_offsets[i + 1] < key_offsets[i]) {
+            set_err("reader_get: key_offsets not ascending at %llu",
+                    (unsigned long long)i);
+            return DBEEL_ERR_INVALID_ARG;
+        }
+    const uint64_t n = n_keys;
+    out->hits = (dbeel_lookup_hit*)malloc((n ? n : 1) * sizeof *out->hits);
+    out->value_offsets = (uint64_t*)calloc(n + 1, sizeof(uint64_t));
+    if (!out->hits || !out->value_offsets) {
+        dbeel_gpu_get_result_free(out);
+        set_err("host malloc failed");
+        return DBEEL_ERR_OOM;
+    }
+    if (n == 0) {
+        out->values = (uint8_t*)malloc(1);
+        return DBEEL_OK;
+    }
+
+    const uint64_t kbytes = key_offsets[n];
+    /* d_batch layout: key offsets (n+1) | value offsets (n+1) | hits (n+1,
+     * the last one zeroed so the scan's final element is the total) */
+    const uint64_t off_bytes = (n + 1) * sizeof(uint64_t);
+    uint64_t* d_koff = nullptr;
+    uint64_t* d_voff = nullptr;
+    dbeel_lookup_hit* d_hits = nullptr;
+    size_t tmp_bytes = 0;
+    uint64_t total = 0;
+    unsigned long long hstats[RS_N] = {};
+    float ms[6] = {};
+    int rc = DBEEL_OK;
+    hipStream_t s = rd->stream;
+
+#define GET_CHECK(call)                                                     \
+    do {                                                                    \
+        hipError_t _e = (call);                                             \
+        if (_e != hipSuccess) {                                             \
+            set_err("%s failed: %s", #call, hipGetErrorString(_e));         \
+            rc = (_e == hipErrorOutOfMemory) ? DBEEL_ERR_OOM                \
+                                             : DBEEL_ERR_HIP;               \
+            goto done;                                                      \
+        }                                                                   \
+    } while (0)
+
+    GET_CHECK(hipSetDevice(rd->device));
+    GET_CHECK(reader_reserve((void**)&rd->d_keys, &rd->keys_cap,
+                             kbytes ? kbytes : 1));
+    GET_CHECK(reader_reserve((void**)&rd->d_batch, &rd->batch_cap,
+                             2 * off_bytes +
+                                 (n + 1) * sizeof(dbeel_lookup_hit)));
+    d_koff = (uint64_t*)rd->d_batch;
+    d_voff = d_koff + (n + 1);
+    d_hits = (dbeel_lookup_hit*)(d_voff + (n + 1));
+    (void)rocprim::exclusive_scan(
+        nullptr, tmp_bytes,
+        rocprim::make_transform_iterator(d_hits, HitValueLen{}), d_voff,
+        (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), s);
+    GET_CHECK(reader_reserve(&rd->d_scantmp, &rd->scantmp_cap,
+                             tmp_bytes ? tmp_bytes : 1));
+
+    GET_CHECK(hipEventRecord(rd->ev[0], s));
+    if (kbytes)
+        GET_CHECK(hipMemcpyAsync(rd->d_keys, keys, kbytes,
+                                 hipMemcpyHostToDevice, s));
+    GET_CHECK(hipMemcpyAsync(d_koff, key_offsets, off_bytes,
+                             hipMemcpyHostToDevice, s));
+    GET_CHECK(hipMemsetAsync(rd->d_stats, 0, RS_N * sizeof(uint64_t), s));
+    GET_CHECK(hipMemsetAsync(d_hits + n, 0, sizeof(dbeel_lookup_hit), s));
+    GET_CHECK(hipEventRecord(rd->ev[1], s));
+    hipLaunchKernelGGL(k_reader_search, dim3(pick_grid(n, READER_BLOCK)),
+                       dim3(READER_BLOCK), 0, s, rd->desc, rd->d_pfx,
+                       rd->d_blooms, rd->d_keys, d_koff, n, d_hits,
+                       rd->d_stats);
+    GET_CHECK(hipEventRecord(rd->ev[2], s));
+    {
+        hipError_t se = rocprim::exclusive_scan(
+            rd->d_scantmp, tmp_bytes,
+            rocprim::make_transform_iterator(d_hits, HitValueLen{}), d_voff,
+            (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), s);
+        GET_CHECK(se);
+    }
+    GET_CHECK(hipEventRecord(rd->ev[3], s));
+    GET_CHECK(hipMemcpyAsync(&total, d_voff + n, 8, hipMemcpyDeviceToHost,
+                             s));
+    GET_CHECK(hipStreamSynchronize(s));
+    GET_CHECK(hipGetLastError());
+    out->values = (uint8_t*)malloc(total ? total : 1);
+    if (!out->values) {
+        set_err("host malloc of %llu value bytes failed",
+                (unsigned long long)total);
+        rc = DBEEL_ERR_OOM;
+        goto done;
+    }
+    if (total)
+        GET_CHECK(reader_reserve((void**)&rd->d_values, &rd->values_cap,
+                                 total));
+    GET_CHECK(hipEventRecord(rd->ev[4], s));
+    if (total)
+        hipLaunchKernelGGL(k_reader_gather, dim3(pick_grid(n * 64, 256)),
+                           dim3(256), 0, s, rd->desc, d_hits, d_voff, n,
+                           rd->d_values);
+    GET_CHECK(hipEventRecord(rd->ev[5], s));
+    GET_CHECK(hipMemcpyAsync(out->hits, d_hits, n * sizeof *out->hits,
+                             hipMemcpyDeviceToHost, s));
+    GET_CHECK(hipMemcpyAsync(out->value_offsets, d_voff, off_bytes,
+                             hipMemcpyDeviceToHost, s));
+    if (total)
+        GET_CHECK(hipMemcpyAsync(out->values, rd->d_values, total,
+                                 hipMemcpyDeviceToHost, s));
+    GET_CHECK(hipMemcpyAsync(hstats, rd->d_stats, sizeof hstats,
+                             hipMemcpyDeviceToHost, s));
+    GET_CHECK(hipEventRecord(rd->ev[6], s));
+    GET_CHECK(hipStreamSynchronize(s));
+    GET_CHECK(hipGetLastError());
+    for (int i = 0; i < 6; i++)
+        GET_CHECK(hipEventElapsedTime(&ms[i], rd->ev[i], rd->ev[i + 1]));
+    out->values_len = total;
+    out->n_keys = n;
+    if (stats) {
+        stats->h2d_ms = ms[0];
+        stats->search_ms = ms[1];
+        stats->gather_ms = ms[2] + ms[4]; /* scan + gather kernel; the
+                                             host gap between them (ms[3],
+                                             sizing the output) is not
+                                             device work */
+        stats->d2h_ms = ms[5];
+        stats->bloom_probes = hstats[RS_PROBES];
+        stats->bloom_skips = hstats[RS_SKIPS];
+        stats->searches = hstats[RS_SEARCHES];
+        stats->hits = hstats[RS_HITS];
+        stats->tombstones = hstats[RS_TOMBS];
+    }
+done:
+    if (rc != DBEEL_OK) {
+        /* nothing of this batch may still be in flight into freed memory */
+        (void)hipStreamSynchronize(s);
+        dbeel_gpu_get_result_free(out);
+    }
+    return rc;
+#undef GET_CHECK
 }
 
 /* ------------------------------------------------------------------ */

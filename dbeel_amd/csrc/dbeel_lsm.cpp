@@ -157,6 +157,64 @@ extern "C" int dbeel_bloom_contains(const uint8_t* bloom_bytes,
     return DBEEL_OK;
 }
 
+/* defined in dbeel_gpu.hip (same library, not exported) */
+extern "C" void dbeel_set_last_error(const char* msg);
+
+extern "C" int dbeel_lsm_reader_open(const char* dir_c, int device,
+                                     dbeel_gpu_reader** out,
+                                     uint64_t* out_indices, size_t* out_n) {
+    if (!dir_c || !out || !out_indices || !out_n) {
+        dbeel_set_last_error("lsm_reader_open: null argument");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    *out = nullptr;
+    *out_n = 0;
+    std::string dir(dir_c);
+    /* a pending journal means a half-swapped directory: the reader must
+     * neither observe it nor complete it (opening never mutates) */
+    if (!scan_indices(dir, "compact_action").empty()) {
+        dbeel_set_last_error("directory has a pending .compact_action "
+                             "journal: run dbeel_lsm_replay first");
+        return DBEEL_ERR_IO;
+    }
+    std::vector<uint64_t> idxs = scan_indices(dir, "index");
+    if (idxs.size() > 64) {
+        dbeel_set_last_error("more than 64 sstables: compact first");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    size_t n = idxs.size();
+    std::vector<std::vector<uint8_t>> datas(n), inds(n), blms(n);
+    std::vector<dbeel_run_view> views(n);
+    std::vector<dbeel_bloom_view> bviews(n);
+    for (size_t i = 0; i < n; i++) {
+        if (!read_whole(file_path(dir, idxs[i], "data"), datas[i]) ||
+            !read_whole(file_path(dir, idxs[i], "index"), inds[i])) {
+            dbeel_set_last_error("cannot read an sstable's data/index file");
+            return DBEEL_ERR_IO;
+        }
+        views[i] = {datas[i].data(), datas[i].size(), inds[i].data(),
+                    inds[i].size()};
+        bviews[i] = {nullptr, 0};
+        std::string bp = file_path(dir, idxs[i], "bloom");
+        if (exists(bp)) {
+            if (!read_whole(bp, blms[i])) {
+                dbeel_set_last_error("cannot read an sstable's bloom file");
+                return DBEEL_ERR_IO;
+            }
+            /* an empty file still counts as a (corrupt) filter */
+            static const uint8_t none = 0;
+            bviews[i] = {blms[i].empty() ? &none : blms[i].data(),
+                         blms[i].size()};
+        }
+    }
+    int rc = dbeel_gpu_reader_open(views.data(), bviews.data(), n, device,
+                                   out);
+    if (rc != DBEEL_OK) return rc;
+    for (size_t i = 0; i < n; i++) out_indices[i] = idxs[i];
+    *out_n = n;
+    return DBEEL_OK;
+}
+
 extern "C" int dbeel_lsm_replay(const char* dir_c, uint32_t* out_replayed) {
     if (!dir_c) return DBEEL_ERR_INVALID_ARG;
     std::string dir(dir_c);

@@ -345,6 +345,211 @@ def lookup(runs, keys, device: int = 0):
     return out
 
 
+HIT_DTYPE = np.dtype(
+    [("run", "<i4"), ("is_tombstone", "<u4"), ("value_offset", "<u8"),
+     ("value_len", "<u8")]
+)
+assert HIT_DTYPE.itemsize == ctypes.sizeof(LookupHit)
+
+
+def _key_blob(keys):
+    """keys -> (u8 blob array, n+1 u64 offsets) in the C ABI's layout."""
+    blob = b"".join(keys)
+    koff = np.zeros(len(keys) + 1, dtype=np.uint64)
+    lens = np.fromiter((len(k) for k in keys), dtype=np.uint64,
+                       count=len(keys))
+    np.cumsum(lens, out=koff[1:])
+    return np.frombuffer(blob or b"\0", dtype=np.uint8), koff
+
+
+def lookup_raw(runs, keys, device: int = 0) -> np.ndarray:
+    """dbeel_gpu_lookup's hit records as a HIT_DTYPE array (run = -1
+    absent, value_offset into runs[run].data) — the field-for-field
+    comparison target of Reader.get_raw."""
+    lib = load()
+    lib.dbeel_gpu_lookup.restype = ctypes.c_int
+    lib.dbeel_gpu_lookup.argtypes = [
+        ctypes.POINTER(RunView), ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint64),
+        ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(LookupHit),
+    ]
+    views, keepalive = _views(runs)
+    ka, koff = _key_blob(keys)
+    hits = np.zeros(len(keys), dtype=HIT_DTYPE)
+    rc = lib.dbeel_gpu_lookup(
+        views, len(runs),
+        ka.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+        koff.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+        len(keys), device,
+        hits.ctypes.data_as(ctypes.POINTER(LookupHit)),
+    )
+    if rc != 0:
+        raise DbeelGpuError(rc, lib.dbeel_gpu_last_error().decode())
+    del keepalive
+    return hits
+
+
+class BloomView(ctypes.Structure):
+    _fields_ = [
+        ("bytes", ctypes.POINTER(ctypes.c_uint8)),
+        ("len", ctypes.c_size_t),
+    ]
+
+
+class GetResult(ctypes.Structure):
+    _fields_ = [
+        ("hits", ctypes.POINTER(LookupHit)),
+        ("value_offsets", ctypes.POINTER(ctypes.c_uint64)),
+        ("values", ctypes.POINTER(ctypes.c_uint8)),
+        ("values_len", ctypes.c_uint64),
+        ("n_keys", ctypes.c_uint64),
+    ]
+
+
+class GetStats(ctypes.Structure):
+    _fields_ = [
+        ("h2d_ms", ctypes.c_double),
+        ("search_ms", ctypes.c_double),
+        ("gather_ms", ctypes.c_double),
+        ("d2h_ms", ctypes.c_double),
+        ("bloom_probes", ctypes.c_uint64),
+        ("bloom_skips", ctypes.c_uint64),
+        ("searches", ctypes.c_uint64),
+        ("hits", ctypes.c_uint64),
+        ("tombstones", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def _load_reader() -> ctypes.CDLL:
+    lib = load()
+    if not hasattr(lib, "_reader_ready"):
+        lib.dbeel_gpu_reader_open.restype = ctypes.c_int
+        lib.dbeel_gpu_reader_open.argtypes = [
+            ctypes.POINTER(RunView), ctypes.POINTER(BloomView),
+            ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
+        ]
+        lib.dbeel_gpu_reader_table_bytes.restype = ctypes.c_uint64
+        lib.dbeel_gpu_reader_table_bytes.argtypes = [ctypes.c_void_p]
+        lib.dbeel_gpu_reader_get.restype = ctypes.c_int
+        lib.dbeel_gpu_reader_get.argtypes = [
+            ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8),
+            ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint64,
+            ctypes.POINTER(GetResult), ctypes.POINTER(GetStats),
+        ]
+        lib.dbeel_gpu_get_result_free.restype = None
+        lib.dbeel_gpu_get_result_free.argtypes = [ctypes.POINTER(GetResult)]
+        lib.dbeel_gpu_reader_close.restype = None
+        lib.dbeel_gpu_reader_close.argtypes = [ctypes.c_void_p]
+        lib._reader_ready = True
+    return lib
+
+
+class Reader:
+    """Resident table reader (LSMTree::get over the sstables,
+    lsm_tree.rs:674-723): runs [(data, index), ...] and their optional
+    "DBLM" filters (blooms[r] = the .bloom file's bytes, or None) are
+    uploaded once; every get() after that moves only keys in and hits +
+    packed values out. No host copy of the runs is needed afterwards."""
+
+    def __init__(self, runs, blooms=None, device: int = 0):
+        self._lib = _load_reader()
+        self._h = None
+        views, keepalive = _views(runs)
+        bviews = None
+        if blooms is not None:
+            if len(blooms) != len(runs):
+                raise ValueError("blooms must be None or one per run")
+            bviews = (BloomView * len(runs))()
+            for i, b in enumerate(blooms):
+                if b is None:
+                    continue
+                a = np.frombuffer(bytes(b) or b"\0", dtype=np.uint8)
+                keepalive.append(a)
+                bviews[i].bytes = a.ctypes.data_as(
+                    ctypes.POINTER(ctypes.c_uint8))
+                bviews[i].len = len(b)
+        h = ctypes.c_void_p()
+        rc = self._lib.dbeel_gpu_reader_open(
+            views, bviews, len(runs), device, ctypes.byref(h)
+        )
+        del keepalive  # open has copied everything to the device
+        if rc != 0:
+            raise DbeelGpuError(rc, self._lib.dbeel_gpu_last_error().decode())
+        self._h = h
+
+    @classmethod
+    def _from_handle(cls, handle) -> "Reader":
+        self = cls.__new__(cls)
+        self._lib = _load_reader()
+        self._h = handle
+        return self
+
+    @property
+    def table_bytes(self) -> int:
+        """Device bytes held between calls: slab + prefixes + bitmaps."""
+        return int(self._lib.dbeel_gpu_reader_table_bytes(self._h))
+
+    def get_raw(self, keys):
+        """-> (hits HIT_DTYPE array, value_offsets u64[n+1], values u8
+        array packed in query order, stats dict)."""
+        if not self._h:
+            raise ValueError("reader is closed")
+        ka, koff = _key_blob(keys)
+        res = GetResult()
+        st = GetStats()
+        rc = self._lib.dbeel_gpu_reader_get(
+            self._h,
+            ka.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+            koff.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+            len(keys), ctypes.byref(res), ctypes.byref(st),
+        )
+        if rc != 0:
+            raise DbeelGpuError(rc, self._lib.dbeel_gpu_last_error().decode())
+        try:
+            n = int(res.n_keys)
+            hits = np.empty(n, dtype=HIT_DTYPE)
+            if n:
+                ctypes.memmove(hits.ctypes.data, res.hits,
+                               n * HIT_DTYPE.itemsize)
+            voff = np.ctypeslib.as_array(res.value_offsets,
+                                         shape=(n + 1,)).copy()
+            nv = int(res.values_len)
+            values = (np.ctypeslib.as_array(res.values, shape=(nv,)).copy()
+                      if nv else np.zeros(0, dtype=np.uint8))
+        finally:
+            self._lib.dbeel_gpu_get_result_free(ctypes.byref(res))
+        return hits, voff, values, st.as_dict()
+
+    def get(self, keys):
+        """lookup()'s convention: value bytes, b"" for a deleted key
+        (tombstone), None if absent."""
+        hits, voff, values, _ = self.get_raw(keys)
+        blob = values.tobytes()
+        off = voff.tolist()
+        return [None if r < 0 else blob[off[q] : off[q + 1]]
+                for q, r in enumerate(hits["run"].tolist())]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.dbeel_gpu_reader_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def encode_run(entries, device: int = 0):
     """GPU run encoder (the memtable-flush path, lsm_tree.rs:925-946):
     entries = iterable of (key: bytes, data: bytes, timestamp: int),
@@ -442,6 +647,32 @@ class Job:
         finally:
             self._lib.dbeel_gpu_result_free(ctypes.byref(res))
         return data, index, n
+
+    def bloom(self) -> bytes:
+        """The "DBLM" filter over the last run()'s surviving keys, built
+        on the device (the .bloom file's bytes, include/dbeel_lsm.h)."""
+        lib = self._lib
+        if not hasattr(lib, "_bloom_ready"):
+            lib.dbeel_gpu_job_bloom.restype = ctypes.c_int
+            lib.dbeel_gpu_job_bloom.argtypes = [
+                ctypes.c_void_p,
+                ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)),
+                ctypes.POINTER(ctypes.c_uint64),
+            ]
+            lib.dbeel_gpu_bloom_free.restype = None
+            lib.dbeel_gpu_bloom_free.argtypes = [
+                ctypes.POINTER(ctypes.c_uint8)]
+            lib._bloom_ready = True
+        p = ctypes.POINTER(ctypes.c_uint8)()
+        n = ctypes.c_uint64()
+        rc = lib.dbeel_gpu_job_bloom(self._h, ctypes.byref(p),
+                                     ctypes.byref(n))
+        if rc != 0:
+            raise DbeelGpuError(rc, lib.dbeel_gpu_last_error().decode())
+        try:
+            return _ptr_bytes(p, int(n.value))
+        finally:
+            lib.dbeel_gpu_bloom_free(p)
 
     def close(self):
         if getattr(self, "_h", None):

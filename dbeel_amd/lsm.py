@@ -113,6 +113,31 @@ def bloom_contains(bloom_bytes: bytes, key: bytes) -> bool:
     return bool(out.value)
 
 
+def open_reader(dir: str, device: int = 0):
+    """Open a resident engine.Reader over every live sstable in dir (with
+    its .bloom where one exists). Returns (reader, indices): indices[r] is
+    the sstable index behind hit run r, ascending. Refuses a directory
+    with a pending .compact_action journal (IO: replay first) or more
+    than 64 sstables (INVALID_ARG: compact first); never mutates it."""
+    from .engine import Reader
+
+    lib = load()
+    if not hasattr(lib, "_lsm_reader_ready"):
+        lib.dbeel_lsm_reader_open.restype = ctypes.c_int
+        lib.dbeel_lsm_reader_open.argtypes = [
+            ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
+            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_size_t),
+        ]
+        lib._lsm_reader_ready = True
+    h = ctypes.c_void_p()
+    idx = (ctypes.c_uint64 * 64)()
+    n = ctypes.c_size_t()
+    rc = lib.dbeel_lsm_reader_open(dir.encode(), device, ctypes.byref(h),
+                                   idx, ctypes.byref(n))
+    _check(rc, lib)
+    return Reader._from_handle(h), [int(idx[i]) for i in range(n.value)]
+
+
 def write_run_files(dir: str, index: int, data: bytes, idx: bytes) -> None:
     """Write {index:020}.data/.index (test/bench helper)."""
     os.makedirs(dir, exist_ok=True)

@@ -138,6 +138,77 @@ int dbeel_gpu_lookup(const dbeel_run_view* runs, size_t n_runs,
                      const uint8_t* keys, const uint64_t* key_offsets,
                      uint64_t n_keys, int device, dbeel_lookup_hit* out);
 
+/* ---- Resident table reader (the read-path seam) ----
+ * LSMTree::get over the sstables (lsm_tree.rs:674-723) with the tables
+ * resident in HBM: open uploads the runs (and their "DBLM" filters,
+ * format in include/dbeel_lsm.h) once; every get after that moves only
+ * the query keys in and the hits + packed value bytes out.
+ *
+ * Results are exactly dbeel_gpu_lookup's (newest run index first, first
+ * key match wins, run = -1 absent, a tombstone is found with
+ * is_tombstone = 1 / value_len = 0, value_offset indexes runs[run].data);
+ * the value bytes of query q are additionally delivered at
+ * values[value_offsets[q] .. value_offsets[q+1]). A run that has a filter
+ * is searched only when the filter answers "maybe" — the reference
+ * consults each sstable's bloom inside the same newest-first loop
+ * (lsm_tree.rs:692-696); the device decision equals dbeel_bloom_contains
+ * on the same bytes.
+ *
+ * open validates arguments (runs as for jobs, n_runs <= 64, device >= 0,
+ * every filter's magic/version/length — a bad filter is
+ * DBEEL_ERR_CORRUPT) before any device call, then uploads, then runs a
+ * device pass that validates every entry, checks that each run is
+ * strictly ascending by key and builds the dense 8-byte key-prefix array
+ * the search runs on; any violation is DBEEL_ERR_CORRUPT.
+ *
+ * A reader holds the padded run slab, 8 B per entry of prefixes, the
+ * filter bitmaps (dbeel_gpu_reader_table_bytes reports their sum) and
+ * per-batch scratch that grows on demand and is reused — no compaction
+ * buffers. One thread at a time per reader; distinct readers are
+ * independent. */
+typedef struct {
+    const uint8_t* bytes;     /* whole .bloom file; NULL = run has no filter */
+    size_t         len;
+} dbeel_bloom_view;
+
+typedef struct dbeel_gpu_reader dbeel_gpu_reader;
+
+int dbeel_gpu_reader_open(const dbeel_run_view* runs,
+                          const dbeel_bloom_view* blooms /* NULL or n_runs */,
+                          size_t n_runs, int device, dbeel_gpu_reader** out);
+/* Device bytes held between calls: slab + prefixes + bitmaps. */
+uint64_t dbeel_gpu_reader_table_bytes(const dbeel_gpu_reader* reader);
+
+/* Engine-allocated; free with dbeel_gpu_get_result_free. */
+typedef struct {
+    dbeel_lookup_hit* hits;          /* n_keys                              */
+    uint64_t*         value_offsets; /* n_keys+1, exclusive; absent or
+                                        tombstone = empty range            */
+    uint8_t*          values;        /* packed in query order               */
+    uint64_t          values_len, n_keys;
+} dbeel_get_result;
+
+/* Per-call evidence. Times are HIP events on the reader's stream:
+ * search_ms is the search kernel alone, gather_ms the value-offset scan
+ * plus the gather kernel. bloom_probes = filter checks performed,
+ * bloom_skips = checks that answered "absent", searches = binary searches
+ * performed, so searches = (bloom_probes - bloom_skips) + visits to
+ * unfiltered runs. hits counts found keys (tombstones included),
+ * tombstones those found deleted. */
+typedef struct {
+    double   h2d_ms, search_ms, gather_ms, d2h_ms;
+    uint64_t bloom_probes, bloom_skips, searches, hits, tombstones;
+} dbeel_get_stats;
+
+/* keys: concatenated blob + n_keys+1 ascending offsets. Zero-length and
+ * duplicate keys are legal; n_keys == 0 succeeds with empty outputs. */
+int dbeel_gpu_reader_get(dbeel_gpu_reader* reader, const uint8_t* keys,
+                         const uint64_t* key_offsets, uint64_t n_keys,
+                         dbeel_get_result* out,
+                         dbeel_get_stats* stats /* may be NULL */);
+void dbeel_gpu_get_result_free(dbeel_get_result* r);
+void dbeel_gpu_reader_close(dbeel_gpu_reader* reader);
+
 /* ---- Run encoder (the memtable-flush path) ----
  * Encodes an already-sorted (key, value, timestamp) stream into a run:
  * the same entry layout + 16-byte index records flush_memtable_to_disk /

@@ -77,6 +77,19 @@ int dbeel_lsm_major_compact(const char* dir, int device,
 int dbeel_bloom_contains(const uint8_t* bloom_bytes, size_t bloom_len,
                          const uint8_t* key, size_t key_len, int* out);
 
+/* Open a resident reader (include/dbeel_gpu.h) over every live sstable in
+ * dir: discovers {i:020}.index in ascending order, reads .data/.index and
+ * the .bloom when it exists. out_indices (capacity 64) maps hit.run back
+ * to the sstable index; *out_n is the number of runs. Never mutates the
+ * directory: a pending {n:020}.compact_action journal returns
+ * DBEEL_ERR_IO (replay first), more than 64 sstables
+ * DBEEL_ERR_INVALID_ARG (compact first). Close with
+ * dbeel_gpu_reader_close. */
+struct dbeel_gpu_reader;
+int dbeel_lsm_reader_open(const char* dir, int device,
+                          struct dbeel_gpu_reader** out,
+                          uint64_t* out_indices, size_t* out_n);
+
 #ifdef __cplusplus
 }
 #endif

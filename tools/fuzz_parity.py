@@ -98,6 +98,65 @@ def random_scan_filter(rng):
     return kw
 
 
+def reader_trial(rng, runs, device):
+    """Resident reader vs the host model of the reference read path
+    (highest run index wins, b"" = deleted, None = absent), with the
+    engine's own filters on a random subset of the runs. Queries: stored
+    keys, their one-byte mutations and extensions, and random keys.
+    Returns a mismatch description or None."""
+    from dbeel_amd import lsm
+    from dbeel_amd.engine import Job, Reader
+    from dbeel_amd.format import parse_run
+
+    model = {}
+    for r, (d, i) in enumerate(runs):
+        for e in parse_run(d, i):
+            model[e.key] = (r, e.data)
+    blooms = []
+    for run in runs:
+        if rng.random() < 0.6:
+            with Job([run], device=device) as job:
+                job.run(True)
+                blooms.append(job.bloom())
+        else:
+            blooms.append(None)
+    stored = list(model)
+    queries = []
+    for _ in range(int(rng.integers(0, 800))):
+        pick = rng.random()
+        k = stored[int(rng.integers(0, len(stored)))] if stored else b""
+        if pick < 0.5:
+            queries.append(k)
+        elif pick < 0.65:
+            queries.append(k + b"\x00")
+        elif pick < 0.8 and k:
+            queries.append(k[:-1] + bytes([k[-1] ^ 1]))
+        elif pick < 0.9:
+            queries.append(k[: len(k) // 2])
+        else:
+            queries.append(bytes(rng.integers(
+                0, 256, int(rng.integers(0, 40)), dtype=np.uint8)))
+    exp = [model[k][1] if k in model else None for k in queries]
+    with Reader(runs, blooms=blooms, device=device) as rd:
+        got = rd.get(queries)
+        _, _, _, st = rd.get_raw(queries)
+    if got != exp:
+        bad = next(i for i, (g, e) in enumerate(zip(got, exp)) if g != e)
+        return f"key {queries[bad].hex()} got {got[bad]} want {exp[bad]}"
+    filtered = [b for b in blooms if b is not None]
+    if len(filtered) == len(runs):
+        if st["searches"] + st["bloom_skips"] != st["bloom_probes"]:
+            return f"stats do not add up: {st}"
+    # zero false negatives: a filter never hides a stored key
+    for r, (d, i) in enumerate(runs):
+        if blooms[r] is None:
+            continue
+        for e in parse_run(d, i)[::17]:
+            if not lsm.bloom_contains(blooms[r], e.key):
+                return f"filter of run {r} misses stored key {e.key.hex()}"
+    return None
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--trials", type=int, default=100)
@@ -105,6 +164,9 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--scan", action="store_true",
                     help="also fuzz dbeel_gpu_scan vs the AsyncIter model")
+    ap.add_argument("--reader", action="store_true",
+                    help="also fuzz the resident reader vs the host model "
+                         "of the read path")
     args = ap.parse_args()
 
     if args.scan:
@@ -133,6 +195,11 @@ def main():
             if (sd, si, sn) != (md, mi, mn):
                 failures += 1
                 print(f"TRIAL {t} SCAN MISMATCH {kw}: n {sn} vs {mn}")
+        if args.reader:
+            why = reader_trial(rng, runs, args.device)
+            if why:
+                failures += 1
+                print(f"TRIAL {t} READER MISMATCH: {why}")
         if (t + 1) % 25 == 0:
             print(f"{t + 1}/{args.trials} trials OK")
     if failures:

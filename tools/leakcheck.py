@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Device-memory stability check: churn job create/run/fetch/destroy,
 streamed ingests (each creates ~per-chunk HIP events), batched jobs,
-scans and sliced compactions, reporting hipMemGetInfo drift. A leak in
+scans, sliced compactions and resident readers (open / get x N / close),
+reporting hipMemGetInfo drift. A leak in
 any path shows as monotonically shrinking free memory.
 
     python tools/leakcheck.py --iters 40
@@ -19,6 +20,7 @@ import dbeel_amd  # noqa: E402
 from dbeel_amd.engine import (  # noqa: E402
     BatchJob,
     Job,
+    Reader,
     compact_sliced,
     load,
     pin_host,
@@ -54,6 +56,13 @@ def main():
         pin_host(d)
         pin_host(i)
 
+    probe_rng = np.random.default_rng(5)
+    probe_keys = [bytes(probe_rng.integers(0, 256, 16, dtype=np.uint8))
+                  for _ in range(10_000)]
+    for d, i in runs:  # half present, half absent
+        recs = np.frombuffer(i, dtype="<u8").reshape(-1, 2)[:2500, 0]
+        probe_keys += [d[int(o) + 8 : int(o) + 24].tobytes() for o in recs]
+
     os.environ["DBEEL_STREAM_CHUNK_MB"] = "1"
     base = None
     total_in = sum(d.nbytes + i.nbytes for d, i in runs)
@@ -74,6 +83,14 @@ def main():
             scan(runs, hash_ranges=[(0, 1 << 31)], device=0)
             compact_sliced(runs, keep_tombstones=True, device=0,
                            max_resident_bytes=total_in // 3)
+            # resident reader: open / get x N (scratch regrowth) / close
+            with Job(runs[:1], device=0) as job:
+                job.run(True)
+                bloom0 = job.bloom()
+            with Reader(runs, blooms=[bloom0, None, None, None],
+                        device=0) as rd:
+                for n in (10, 4000, 100, 20_000):
+                    rd.get(probe_keys[:n])
             f = free_mem()
             if base is None:
                 base = f
