@@ -45,7 +45,9 @@
  *   k_reader_*   : the resident table reader (LSMTree::get over the
  *                  sstables, lsm_tree.rs:674-723): open-time validation
  *                  + prefix array, batched search with the on-device
- *                  bloom prefilter, value gather.
+ *                  bloom prefilter, value gather; k_reader_adopt turns
+ *                  a compaction output into a resident table (prefixes
+ *                  + filter bits in one pass) for the live table list.
  *   host side    : resident jobs, batched independent jobs (one launch
  *                  set, per-job output slicing), streamed pinned ingest
  *                  with copy/compute overlap, sliced compaction for
@@ -1228,6 +1230,9 @@ struct dbeel_gpu_job {
                            pipeline per step. */
     RunsDesc desc{};
     uint8_t* d_input = nullptr; /* one slab: all run data+index            */
+    bool borrowed = false;      /* desc points at device memory owned by a
+                                   resident reader: no slab, never freed
+                                   here, ingest refused                    */
     RankRec* d_rank = nullptr;
     uint64_t* d_dstoff = nullptr;
     uint32_t* d_pos = nullptr;
@@ -1300,9 +1305,15 @@ static int validate_runs(const dbeel_run_view* runs, size_t n_runs) {
     return DBEEL_OK;
 }
 
+/* borrowed: runs[].data / .index are DEVICE pointers on `device` that
+ * stay valid (and padded like a slab) for the job's lifetime; nothing is
+ * uploaded. Nothing in the pipeline needs one contiguous slab: k_emit
+ * stores absolute source addresses, the pair table and the aux tier
+ * depend only on counts and key sizes. */
 static int job_create_impl(const dbeel_run_view* runs, size_t n_runs,
                            const uint32_t* runs_per_job, size_t n_jobs,
-                           int device, dbeel_gpu_job** out_job) {
+                           int device, dbeel_gpu_job** out_job,
+                           bool borrowed = false) {
     g_err[0] = 0;
     if (!out_job) {
         set_err("out_job is null");
@@ -1344,6 +1355,7 @@ static int job_create_impl(const dbeel_run_view* runs, size_t n_runs,
     dbeel_gpu_job* job = new (std::nothrow) dbeel_gpu_job();
     if (!job) return DBEEL_ERR_OOM;
     job->device = device;
+    job->borrowed = borrowed;
 
     uint64_t input_bytes = 0, total = 0, total_data = 0;
     for (size_t r = 0; r < n_runs; r++) {
@@ -1371,7 +1383,9 @@ static int job_create_impl(const dbeel_run_view* runs, size_t n_runs,
 
     /* +-16 B padding: the copy kernel's aligned-base loads may touch up
      * to 15 B before/after an entry's bytes */
-    JOB_CHECK(hipMalloc(&job->d_input, (input_bytes ? input_bytes : 16) + 32));
+    if (!borrowed)
+        JOB_CHECK(hipMalloc(&job->d_input,
+                            (input_bytes ? input_bytes : 16) + 32));
     uint64_t n = total ? total : 1;
     JOB_CHECK(hipMalloc(&job->d_rank, n * sizeof(RankRec)));
     JOB_CHECK(hipMalloc(&job->d_dstoff, n * sizeof(uint64_t)));
@@ -1410,7 +1424,7 @@ static int job_create_impl(const dbeel_run_view* runs, size_t n_runs,
 
     /* Upload: one slab; record per-run device pointers. */
     JOB_CHECK(hipEventRecord(job->ev[0], job->stream));
-    uint8_t* p = job->d_input + 16;
+    uint8_t* p = borrowed ? nullptr : job->d_input + 16;
     RunsDesc& D = job->desc;
     memset(&D, 0, sizeof D);
     D.n_runs = (int)n_runs;
@@ -1427,16 +1441,16 @@ static int job_create_impl(const dbeel_run_view* runs, size_t n_runs,
     }
     uint64_t base = 0;
     for (size_t r = 0; r < n_runs; r++) {
-        D.data[r] = p;
+        D.data[r] = borrowed ? runs[r].data : p;
         D.data_len[r] = runs[r].data_len;
-        if (runs[r].data_len) {
+        if (runs[r].data_len && !borrowed) {
             JOB_CHECK(hipMemcpyAsync(p, runs[r].data, runs[r].data_len,
                                      hipMemcpyHostToDevice, job->stream));
             p += runs[r].data_len;
         }
-        D.index[r] = p;
+        D.index[r] = borrowed ? runs[r].index : p;
         D.count[r] = runs[r].index_len / 16;
-        if (runs[r].index_len) {
+        if (runs[r].index_len && !borrowed) {
             JOB_CHECK(hipMemcpyAsync(p, runs[r].index, runs[r].index_len,
                                      hipMemcpyHostToDevice, job->stream));
             p += runs[r].index_len;
@@ -1506,7 +1520,7 @@ static int job_create_impl(const dbeel_run_view* runs, size_t n_runs,
     JOB_CHECK(hipStreamSynchronize(job->stream));
     float ms = 0;
     JOB_CHECK(hipEventElapsedTime(&ms, job->ev[0], job->ev[1]));
-    job->h2d_ms = ms;
+    job->h2d_ms = borrowed ? 0.0 : ms;
 
     /* pick the aux tier from the max key_size (index slabs are resident
      * now); the tier is a traffic optimization only — every tier is
@@ -1646,7 +1660,7 @@ extern "C" int dbeel_gpu_job_fetch_job(dbeel_gpu_job* job, size_t job_idx,
 extern "C" void dbeel_gpu_job_destroy(dbeel_gpu_job* job) {
     if (!job) return;
     if (job->device >= 0) hipSetDevice(job->device);
-    hipFree(job->d_input);
+    hipFree(job->d_input); /* null for a borrowed-input job */
     hipFree(job->d_rank);
     hipFree(job->d_dstoff);
     hipFree(job->d_pos);
@@ -1706,6 +1720,10 @@ extern "C" int dbeel_gpu_job_ingest(dbeel_gpu_job* job,
     g_err[0] = 0;
     if (!job || !runs) {
         set_err("job_ingest: null argument");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (job->borrowed) {
+        set_err("job_ingest: the job's inputs belong to a resident reader");
         return DBEEL_ERR_INVALID_ARG;
     }
     if ((int)n_runs != job->desc.n_runs) {
@@ -2161,6 +2179,16 @@ extern "C" int dbeel_gpu_job_run(dbeel_gpu_job* job, int keep_tombstones,
 /* with a splitmix64 finalizer, identical to dbeel_lsm.cpp's checker. */
 /* ------------------------------------------------------------------ */
 
+/* splitmix64 finalizer */
+__device__ __forceinline__ uint64_t d_mix64(uint64_t h) {
+    h ^= h >> 30;
+    h *= 0xbf58476d1ce4e5b9ull;
+    h ^= h >> 27;
+    h *= 0x94d049bb133111ebull;
+    h ^= h >> 31;
+    return h;
+}
+
 __device__ __forceinline__ uint64_t d_fnv1a64(const uint8_t* p, uint64_t n,
                                               uint64_t seed) {
     uint64_t h = 1469598103934665603ull ^ seed;
@@ -2168,12 +2196,7 @@ __device__ __forceinline__ uint64_t d_fnv1a64(const uint8_t* p, uint64_t n,
         h ^= p[i];
         h *= 1099511628211ull;
     }
-    h ^= h >> 30;
-    h *= 0xbf58476d1ce4e5b9ull;
-    h ^= h >> 27;
-    h *= 0x94d049bb133111ebull;
-    h ^= h >> 31;
-    return h;
+    return d_mix64(h);
 }
 
 __global__ void k_bloom(const uint8_t* out_data, const uint8_t* out_index,
@@ -2405,10 +2428,10 @@ extern "C" int dbeel_gpu_lookup(const dbeel_run_view* runs, size_t n_runs,
 /* Resident table reader                                              */
 /*                                                                    */
 /* dbeel_gpu_lookup above answers one batch by building a whole       */
-/* compaction job. The reader keeps what a read needs resident — the  */
-/* padded run slab, one dense big-endian 8-byte key prefix per entry  */
-/* and the runs' "DBLM" filter bitmaps — and answers any number of    */
-/* batches against it:                                                */
+/* compaction job. The reader keeps what a read needs resident — per  */
+/* run one table: the padded run bytes, one dense big-endian 8-byte   */
+/* key prefix per entry and the run's "DBLM" filter bitmap — and      */
+/* answers any number of batches against the table list:              */
 /*   k_reader_prepare : open-time pass; k_prepare's checks (bounds,   */
 /*                      bincode field cross-check, monotone offsets)  */
 /*                      plus strict key order inside each run, and    */
@@ -2422,6 +2445,10 @@ extern "C" int dbeel_gpu_lookup(const dbeel_run_view* runs, size_t n_runs,
 /*                      key compares on the blob.                     */
 /*   rocPRIM scan     : value_len -> exclusive value offsets.         */
 /*   k_reader_gather  : wave per hit, 8-B chunks, exact-length reads. */
+/*   k_reader_adopt   : a compaction output copied device-to-device   */
+/*                      into a new table gets its prefixes and filter */
+/*                      bits in one pass (no validation: the engine   */
+/*                      just wrote it).                               */
 /* ------------------------------------------------------------------ */
 
 struct ReaderBloom {
@@ -2431,6 +2458,15 @@ struct ReaderBloom {
     uint32_t k;
     uint32_t rsv;
 };
+
+/* Per-run prefix arrays (each run is its own resident table). Passed by
+ * value next to RunsDesc: 2.7 KiB + 0.5 KiB stays under the 4 KiB
+ * kernel-argument limit. */
+struct ReaderPfx {
+    const uint64_t* p[MAX_RUNS];
+};
+static_assert(sizeof(RunsDesc) + sizeof(ReaderPfx) + 64 <= 4096,
+              "k_reader_search arguments must fit the kernarg segment");
 
 /* stats slots of dbeel_get_stats, in order */
 enum { RS_PROBES, RS_SKIPS, RS_SEARCHES, RS_HITS, RS_TOMBS, RS_N };
@@ -2472,7 +2508,7 @@ __global__ void k_reader_prepare(RunsDesc R, uint64_t* pfx, uint32_t* err) {
 }
 
 __global__ __launch_bounds__(READER_BLOCK) void k_reader_search(
-    RunsDesc R, const uint64_t* pfx, const ReaderBloom* blooms,
+    RunsDesc R, ReaderPfx pfx, const ReaderBloom* blooms,
     const uint8_t* keys, const uint64_t* key_off, uint64_t n_keys,
     dbeel_lookup_hit* out, unsigned long long* stats) {
     __shared__ unsigned long long s_stats[RS_N];
@@ -2517,7 +2553,7 @@ __global__ __launch_bounds__(READER_BLOCK) void k_reader_search(
                 }
             }
             c[RS_SEARCHES]++;
-            const uint64_t* P = pfx + R.entry_base[r];
+            const uint64_t* P = pfx.p[r];
             const uint64_t n = R.count[r];
             uint64_t lo = 0, hi = n;
             while (lo < hi) {
@@ -2610,16 +2646,37 @@ __global__ void k_reader_gather(RunsDesc R, const dbeel_lookup_hit* hits,
     }
 }
 
+/* One resident run. d_run is laid out 16 B pad | data | index | 16 B pad:
+ * the padding a job's input slab has, so a compaction job can borrow the
+ * table as its input (k_copy's aligned loads may touch up to 15 B either
+ * side of an entry). */
+struct ReaderTable {
+    uint8_t* d_run = nullptr;
+    uint64_t* d_pfx = nullptr;  /* dense big-endian key prefixes         */
+    uint8_t* d_bits = nullptr;  /* filter bitmap; NULL = run has none    */
+    uint64_t data_len = 0, count = 0;
+    ReaderBloom bloom{};        /* header fields; .bits == d_bits        */
+    uint64_t bytes = 0;         /* requested bytes: run + prefixes + bitmap */
+
+    const uint8_t* data() const { return d_run + 16; }
+    const uint8_t* index() const { return d_run + 16 + data_len; }
+};
+
 struct dbeel_gpu_reader {
     int device = -1;
     hipStream_t stream = nullptr;
     hipEvent_t ev[7] = {};
+    /* the table list, in read-path order (highest position wins), and what
+     * the kernels see of it — rebuilt by reader_link on every list edit */
+    std::vector<ReaderTable> tables;
     RunsDesc desc{};
-    uint8_t* d_slab = nullptr;      /* all run data+index, +-16 B padded */
-    uint64_t* d_pfx = nullptr;      /* dense big-endian key prefixes     */
-    uint8_t* d_bitmaps = nullptr;   /* filter bitmaps, 8-B aligned each  */
-    ReaderBloom* d_blooms = nullptr; /* n_runs descriptors               */
-    uint64_t table_bytes = 0;
+    ReaderPfx pfx{};
+    ReaderBloom* d_blooms = nullptr; /* MAX_RUNS descriptors             */
+    /* output of a compaction between begin and commit/abort; gets do not
+     * see it */
+    bool has_pending = false;
+    ReaderTable pending;
+    std::vector<uint32_t> pending_pos; /* its input tables, ascending    */
     /* per-batch scratch, grown on demand and reused */
     uint8_t* d_keys = nullptr;
     uint64_t keys_cap = 0;
@@ -2643,13 +2700,97 @@ static hipError_t reader_reserve(void** p, uint64_t* cap, uint64_t need) {
     return e;
 }
 
+static void table_free(ReaderTable& t) {
+    (void)hipFree(t.d_run);
+    (void)hipFree(t.d_pfx);
+    (void)hipFree(t.d_bits);
+    t = ReaderTable();
+}
+
+/* bitmaps are whole 8-B words: k_reader_adopt sets bits through 4-B words */
+static inline uint64_t bitmap_bytes(uint64_t n_bits) {
+    return ((n_bits + 7) / 8 + 7) & ~7ull;
+}
+
+/* Right-sized allocations for one run; n_bits = 0 means no filter. On
+ * failure t is left empty. */
+static hipError_t table_alloc(ReaderTable& t, uint64_t data_len,
+                              uint64_t count, uint64_t n_bits) {
+    const uint64_t payload = data_len + count * 16;
+    const uint64_t run_bytes = (payload ? payload : 16) + 32;
+    const uint64_t pfx_bytes = (count ? count : 1) * sizeof(uint64_t);
+    const uint64_t bm_bytes = n_bits ? bitmap_bytes(n_bits) : 0;
+    t = ReaderTable();
+    hipError_t e = hipMalloc(&t.d_run, run_bytes);
+    if (e == hipSuccess) e = hipMalloc(&t.d_pfx, pfx_bytes);
+    if (e == hipSuccess && bm_bytes) e = hipMalloc(&t.d_bits, bm_bytes);
+    if (e != hipSuccess) {
+        table_free(t);
+        return e;
+    }
+    t.data_len = data_len;
+    t.count = count;
+    t.bytes = run_bytes + pfx_bytes + bm_bytes;
+    return hipSuccess;
+}
+
+static RunsDesc table_desc(const ReaderTable& t) {
+    RunsDesc D;
+    memset(&D, 0, sizeof D);
+    D.n_runs = 1;
+    D.total = t.count;
+    D.data[0] = t.data();
+    D.index[0] = t.index();
+    D.data_len[0] = t.data_len;
+    D.count[0] = t.count;
+    D.job_hi[0] = 1;
+    return D;
+}
+
+/* Rebuilds the descriptors from the table list and uploads the filter
+ * descriptors. The reader's stream is idle between calls, so nothing reads
+ * d_blooms while it is rewritten. */
+static hipError_t reader_link(dbeel_gpu_reader* rd) {
+    ReaderBloom hb[MAX_RUNS];
+    memset(hb, 0, sizeof hb);
+    RunsDesc& D = rd->desc;
+    memset(&D, 0, sizeof D);
+    memset(&rd->pfx, 0, sizeof rd->pfx);
+    D.n_runs = (int)rd->tables.size();
+    uint64_t base = 0;
+    for (size_t r = 0; r < rd->tables.size(); r++) {
+        const ReaderTable& t = rd->tables[r];
+        D.data[r] = t.data();
+        D.index[r] = t.index();
+        D.data_len[r] = t.data_len;
+        D.count[r] = t.count;
+        D.entry_base[r] = base;
+        base += t.count;
+        rd->pfx.p[r] = t.d_pfx;
+        hb[r] = t.bloom;
+        hb[r].bits = t.d_bits;
+    }
+    D.total = base;
+    hipError_t e = hipMemcpyAsync(rd->d_blooms, hb, sizeof hb,
+                                  hipMemcpyHostToDevice, rd->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(rd->stream);
+    return e;
+}
+
+extern "C" void dbeel_gpu_reader_compact_abort(dbeel_gpu_reader* rd) {
+    if (!rd || !rd->has_pending) return;
+    if (rd->device >= 0) (void)hipSetDevice(rd->device);
+    table_free(rd->pending);
+    rd->pending_pos.clear();
+    rd->has_pending = false;
+}
+
 extern "C" void dbeel_gpu_reader_close(dbeel_gpu_reader* rd) {
     if (!rd) return;
     if (rd->device >= 0) (void)hipSetDevice(rd->device);
     if (rd->stream) (void)hipStreamSynchronize(rd->stream);
-    (void)hipFree(rd->d_slab);
-    (void)hipFree(rd->d_pfx);
-    (void)hipFree(rd->d_bitmaps);
+    dbeel_gpu_reader_compact_abort(rd);
+    for (ReaderTable& t : rd->tables) table_free(t);
     (void)hipFree(rd->d_blooms);
     (void)hipFree(rd->d_keys);
     (void)hipFree(rd->d_batch);
@@ -2663,7 +2804,20 @@ extern "C" void dbeel_gpu_reader_close(dbeel_gpu_reader* rd) {
 }
 
 extern "C" uint64_t dbeel_gpu_reader_table_bytes(const dbeel_gpu_reader* rd) {
-    return rd ? rd->table_bytes : 0;
+    if (!rd) return 0;
+    uint64_t sum = rd->has_pending ? rd->pending.bytes : 0;
+    for (const ReaderTable& t : rd->tables) sum += t.bytes;
+    return sum;
+}
+
+extern "C" size_t dbeel_gpu_reader_run_count(const dbeel_gpu_reader* rd) {
+    return rd ? rd->tables.size() : 0;
+}
+
+/* Library-internal (dbeel_lsm.cpp's bloom gate): data bytes of run pos. */
+extern "C" __attribute__((visibility("hidden"))) uint64_t
+dbeel_reader_run_data_len(const dbeel_gpu_reader* rd, size_t pos) {
+    return (rd && pos < rd->tables.size()) ? rd->tables[pos].data_len : 0;
 }
 
 /* "DBLM" header (include/dbeel_lsm.h): magic | ver | k | pad | n_bits |
@@ -2701,6 +2855,47 @@ static int parse_bloom(const dbeel_bloom_view& v, size_t r,
     return DBEEL_OK;
 }
 
+/* Allocates a table for one host run, enqueues its upload and the
+ * k_reader_prepare pass over it (violations are OR-ed into *d_err) on the
+ * reader's stream. hb = the run's parsed filter header, NULL = no filter.
+ * The caller synchronises before the host buffers go away. */
+static hipError_t reader_upload_table(dbeel_gpu_reader* rd,
+                                      const dbeel_run_view& run,
+                                      const dbeel_bloom_view* bloom,
+                                      const ReaderBloom* hb, uint32_t* d_err,
+                                      ReaderTable& t) {
+    hipStream_t s = rd->stream;
+    hipError_t e = table_alloc(t, run.data_len, run.index_len / 16,
+                               hb ? hb->n_bits : 0);
+    if (e != hipSuccess) return e;
+    if (run.data_len)
+        e = hipMemcpyAsync(t.d_run + 16, run.data, run.data_len,
+                           hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && run.index_len)
+        e = hipMemcpyAsync(t.d_run + 16 + run.data_len, run.index,
+                           run.index_len, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && hb) {
+        t.bloom = *hb;
+        t.bloom.bits = t.d_bits;
+        e = hipMemcpyAsync(t.d_bits, bloom->bytes + 32, (hb->n_bits + 7) / 8,
+                           hipMemcpyHostToDevice, s);
+    }
+    if (e == hipSuccess && t.count)
+        hipLaunchKernelGGL(k_reader_prepare, dim3(pick_grid(t.count, 256)),
+                           dim3(256), 0, s, table_desc(t), t.d_pfx, d_err);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(s);
+        table_free(t);
+    }
+    return e;
+}
+
+static void set_err_prepare(uint32_t err) {
+    set_err(err & DERR_CORRUPT
+                ? "corrupt input run (entry bounds/fields)"
+                : "input run is not strictly ascending by key");
+}
+
 extern "C" int dbeel_gpu_reader_open(const dbeel_run_view* runs,
                                      const dbeel_bloom_view* blooms,
                                      size_t n_runs, int device,
@@ -2718,15 +2913,11 @@ extern "C" int dbeel_gpu_reader_open(const dbeel_run_view* runs,
         return DBEEL_ERR_INVALID_ARG;
     }
     ReaderBloom hb[MAX_RUNS];
-    uint64_t bm_off[MAX_RUNS];
-    uint64_t bitmap_bytes = 0;
     memset(hb, 0, sizeof hb);
     for (size_t r = 0; r < n_runs; r++) {
-        bm_off[r] = bitmap_bytes;
         if (!blooms || !blooms[r].bytes) continue;
         rc = parse_bloom(blooms[r], r, &hb[r]);
         if (rc) return rc;
-        bitmap_bytes += ((hb[r].n_bits + 7) / 8 + 7) & ~7ull;
     }
 
     int ndev = 0;
@@ -2753,81 +2944,343 @@ extern "C" int dbeel_gpu_reader_open(const dbeel_run_view* runs,
         }                                                                   \
     } while (0)
 
-    uint64_t input_bytes = 0, total = 0;
-    for (size_t r = 0; r < n_runs; r++) {
-        input_bytes += runs[r].data_len + runs[r].index_len;
-        total += runs[r].index_len / 16;
-    }
-    const uint64_t slab_bytes = (input_bytes ? input_bytes : 16) + 32;
-    const uint64_t pfx_bytes = (total ? total : 1) * sizeof(uint64_t);
     uint32_t* d_err = nullptr;
     uint32_t err = 0;
 
     RD_CHECK(hipStreamCreate(&rd->stream));
     for (int i = 0; i < 7; i++) RD_CHECK(hipEventCreate(&rd->ev[i]));
-    /* same +-16 B padding as a job's input slab */
-    RD_CHECK(hipMalloc(&rd->d_slab, slab_bytes));
-    RD_CHECK(hipMalloc(&rd->d_pfx, pfx_bytes));
-    RD_CHECK(hipMalloc(&rd->d_bitmaps, bitmap_bytes ? bitmap_bytes : 8));
     RD_CHECK(hipMalloc(&rd->d_blooms, MAX_RUNS * sizeof(ReaderBloom)));
     RD_CHECK(hipMalloc(&rd->d_stats, (RS_N + 1) * sizeof(uint64_t)));
-    rd->table_bytes = slab_bytes + pfx_bytes + bitmap_bytes;
     d_err = (uint32_t*)(rd->d_stats + RS_N);
-
-    {
-        uint8_t* p = rd->d_slab + 16;
-        RunsDesc& D = rd->desc;
-        memset(&D, 0, sizeof D);
-        D.n_runs = (int)n_runs;
-        D.total = total;
-        uint64_t base = 0;
-        for (size_t r = 0; r < n_runs; r++) {
-            D.data[r] = p;
-            D.data_len[r] = runs[r].data_len;
-            if (runs[r].data_len) {
-                RD_CHECK(hipMemcpyAsync(p, runs[r].data, runs[r].data_len,
-                                        hipMemcpyHostToDevice, rd->stream));
-                p += runs[r].data_len;
-            }
-            D.index[r] = p;
-            D.count[r] = runs[r].index_len / 16;
-            if (runs[r].index_len) {
-                RD_CHECK(hipMemcpyAsync(p, runs[r].index, runs[r].index_len,
-                                        hipMemcpyHostToDevice, rd->stream));
-                p += runs[r].index_len;
-            }
-            D.entry_base[r] = base;
-            base += D.count[r];
-            if (blooms && blooms[r].bytes) {
-                uint8_t* b = rd->d_bitmaps + bm_off[r];
-                RD_CHECK(hipMemcpyAsync(b, blooms[r].bytes + 32,
-                                        (hb[r].n_bits + 7) / 8,
-                                        hipMemcpyHostToDevice, rd->stream));
-                hb[r].bits = b;
-            }
-        }
-    }
-    RD_CHECK(hipMemcpyAsync(rd->d_blooms, hb, sizeof hb,
-                            hipMemcpyHostToDevice, rd->stream));
     RD_CHECK(hipMemsetAsync(d_err, 0, sizeof(uint64_t), rd->stream));
-    if (total)
-        hipLaunchKernelGGL(k_reader_prepare, dim3(pick_grid(total, 256)),
-                           dim3(256), 0, rd->stream, rd->desc, rd->d_pfx,
-                           d_err);
+    rd->tables.reserve(MAX_RUNS);
+    for (size_t r = 0; r < n_runs; r++) {
+        const bool filtered = blooms && blooms[r].bytes;
+        ReaderTable t;
+        RD_CHECK(reader_upload_table(rd, runs[r],
+                                     filtered ? &blooms[r] : nullptr,
+                                     filtered ? &hb[r] : nullptr, d_err, t));
+        rd->tables.push_back(t);
+    }
     RD_CHECK(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost,
                             rd->stream));
-    /* hb and the caller's buffers are read by the async copies above */
+    /* the caller's buffers are read by the async copies above */
     RD_CHECK(hipStreamSynchronize(rd->stream));
     RD_CHECK(hipGetLastError());
+    RD_CHECK(reader_link(rd));
 #undef RD_CHECK
     if (err) {
-        set_err(err & DERR_CORRUPT
-                    ? "corrupt input run (entry bounds/fields)"
-                    : "input run is not strictly ascending by key");
+        set_err_prepare(err);
         dbeel_gpu_reader_close(rd);
         return DBEEL_ERR_CORRUPT;
     }
     *out_reader = rd;
+    return DBEEL_OK;
+}
+
+/* ---- Live updates: the shared sstable list of the reference's LSMTree
+ * (flush pushes a table, lsm_tree.rs:901-915; compaction partitions out
+ * its inputs, pushes the output and swaps the list while reads finish on
+ * the old one, lsm_tree.rs:1113-1145). ---- */
+
+extern "C" int dbeel_gpu_reader_insert_run(dbeel_gpu_reader* rd, size_t pos,
+                                           const dbeel_run_view* run,
+                                           const dbeel_bloom_view* bloom) {
+    g_err[0] = 0;
+    if (!rd || !run) {
+        set_err("reader_insert_run: null argument");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (pos > rd->tables.size()) {
+        set_err("reader_insert_run: position %zu past the %zu runs held", pos,
+                rd->tables.size());
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (rd->tables.size() >= MAX_RUNS) {
+        set_err("reader_insert_run: reader already holds %d runs", MAX_RUNS);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    int rc = validate_runs(run, 1);
+    if (rc) return rc;
+    const bool filtered = bloom && bloom->bytes;
+    ReaderBloom hb;
+    memset(&hb, 0, sizeof hb);
+    if (filtered) {
+        rc = parse_bloom(*bloom, pos, &hb);
+        if (rc) return rc;
+    }
+    HIP_CHECK(hipSetDevice(rd->device));
+    uint32_t* d_err = (uint32_t*)(rd->d_stats + RS_N);
+    uint32_t err = 0;
+    HIP_CHECK(hipMemsetAsync(d_err, 0, sizeof(uint64_t), rd->stream));
+    ReaderTable t;
+    hipError_t e = reader_upload_table(rd, *run, filtered ? bloom : nullptr,
+                                       filtered ? &hb : nullptr, d_err, t);
+    if (e == hipSuccess) {
+        e = hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, rd->stream);
+        hipError_t se = hipStreamSynchronize(rd->stream);
+        if (e == hipSuccess) e = se;
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e != hipSuccess) table_free(t);
+    }
+    if (e != hipSuccess) {
+        set_err("reader_insert_run: %s", hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? DBEEL_ERR_OOM : DBEEL_ERR_HIP;
+    }
+    if (err) {
+        set_err_prepare(err);
+        table_free(t);
+        return DBEEL_ERR_CORRUPT;
+    }
+    rd->tables.insert(rd->tables.begin() + pos, t);
+    /* a pending compaction keeps naming the same tables */
+    for (uint32_t& p : rd->pending_pos)
+        if (p >= pos) p++;
+    HIP_CHECK(reader_link(rd));
+    return DBEEL_OK;
+}
+
+/* The device half of "fetch, re-upload, k_reader_prepare, k_bloom" for a
+ * run the engine just produced (no validation): one pass over the index
+ * records writes each entry's big-endian key prefix and, when bits is not
+ * NULL, sets its k filter bits — dbeel_gpu_job_bloom's hash pair, so the
+ * bitmap equals k_bloom's. Each key byte is read once and feeds the prefix
+ * and both hashes. Bit positions are hash-scattered over the whole bitmap,
+ * so the atomics see no systematic contention. */
+__global__ void k_reader_adopt(const uint8_t* data, const uint8_t* index,
+                               uint64_t n, uint64_t* pfx, uint32_t* bits,
+                               uint64_t n_bits, uint64_t seed, uint32_t kk) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += stride) {
+        const uint8_t* rec = index + i * 16;
+        const uint8_t* key = data + ld_u64(rec) + 8;
+        const uint64_t klen = ld_u32(rec + 8) - 8;
+        if (!bits) {
+            pfx[i] = key_prefix(key, klen);
+            continue;
+        }
+        uint64_t v = 0;
+        uint64_t h1 = 1469598103934665603ull ^ seed;
+        uint64_t h2 = 1469598103934665603ull ^ seed ^ 0x9e3779b97f4a7c15ull;
+        for (uint64_t j = 0; j < klen; j++) {
+            const uint64_t c = key[j];
+            if (j < 8) v |= c << (8 * j);
+            h1 = (h1 ^ c) * 1099511628211ull;
+            h2 = (h2 ^ c) * 1099511628211ull;
+        }
+        pfx[i] = __builtin_bswap64(v);
+        h1 = d_mix64(h1);
+        h2 = d_mix64(h2) | 1;
+        for (uint32_t j = 0; j < kk; j++) {
+            uint64_t bit = (h1 + j * h2) % n_bits;
+            atomicOr(&bits[bit >> 5], 1u << (bit & 31));
+        }
+    }
+}
+
+extern "C" int dbeel_gpu_reader_compact_begin(
+    dbeel_gpu_reader* rd, const uint32_t* positions, size_t n_positions,
+    int keep_tombstones, int build_bloom, dbeel_compact_result* out,
+    uint8_t** bloom_bytes, uint64_t* bloom_len,
+    dbeel_reader_compact_stats* stats) {
+    g_err[0] = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (out) memset(out, 0, sizeof *out);
+    if (bloom_bytes) *bloom_bytes = nullptr;
+    if (bloom_len) *bloom_len = 0;
+    if (!rd || !positions || n_positions == 0) {
+        set_err("reader_compact_begin: null reader or no positions");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if ((bloom_bytes == nullptr) != (bloom_len == nullptr)) {
+        set_err("reader_compact_begin: bloom_bytes and bloom_len go together");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (rd->has_pending) {
+        set_err("reader_compact_begin: a compaction is already pending");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    for (size_t i = 0; i < n_positions; i++)
+        if (positions[i] >= rd->tables.size() ||
+            (i && positions[i] <= positions[i - 1])) {
+            set_err("reader_compact_begin: positions must be strictly "
+                    "ascending and below %zu", rd->tables.size());
+            return DBEEL_ERR_INVALID_ARG;
+        }
+    HIP_CHECK(hipSetDevice(rd->device));
+    /* the job reads the tables on its own stream */
+    HIP_CHECK(hipStreamSynchronize(rd->stream));
+
+    dbeel_run_view views[MAX_RUNS];
+    for (size_t i = 0; i < n_positions; i++) {
+        const ReaderTable& t = rd->tables[positions[i]];
+        views[i] = {t.data(), (size_t)t.data_len, t.index(),
+                    (size_t)(t.count * 16)};
+    }
+    dbeel_gpu_job* job = nullptr;
+    uint32_t one[1] = {(uint32_t)n_positions};
+    int rc = job_create_impl(views, n_positions, one, 1, rd->device, &job,
+                             /*borrowed=*/true);
+    if (rc) return rc;
+    uint64_t out_data_len = 0, out_entries = 0;
+    dbeel_compact_timings pt;
+    memset(&pt, 0, sizeof pt);
+    rc = dbeel_gpu_job_run(job, keep_tombstones, &out_data_len, &out_entries,
+                           &pt);
+    if (rc) {
+        dbeel_gpu_job_destroy(job);
+        return rc;
+    }
+
+    /* output -> right-sized resident table, device to device */
+    const uint64_t n_bits =
+        build_bloom
+            ? (uint64_t)(9.585 * (double)(out_entries ? out_entries : 1)) + 64
+            : 0;
+    const uint64_t seed = 0xDBEE1;
+    ReaderTable t;
+    hipStream_t s = job->stream;
+    hipError_t e = table_alloc(t, out_data_len, out_entries, n_bits);
+    float adopt_ms = 0, d2h_ms = 0;
+    uint64_t d2h_bytes = 0;
+    uint8_t* bbuf = nullptr;
+    if (e == hipSuccess) e = hipEventRecord(job->ev[0], s);
+    if (e == hipSuccess && out_data_len)
+        e = hipMemcpyAsync(t.d_run + 16, job->d_outdata, out_data_len,
+                           hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && out_entries)
+        e = hipMemcpyAsync(t.d_run + 16 + out_data_len, job->d_outindex,
+                           out_entries * 16, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && n_bits) {
+        t.bloom.n_bits = n_bits;
+        t.bloom.seed = seed;
+        t.bloom.k = 7;
+        t.bloom.bits = t.d_bits;
+        e = hipMemsetAsync(t.d_bits, 0, bitmap_bytes(n_bits), s);
+    }
+    if (e == hipSuccess && out_entries)
+        hipLaunchKernelGGL(k_reader_adopt, dim3(pick_grid(out_entries, 256)),
+                           dim3(256), 0, s, t.data(), t.index(), out_entries,
+                           t.d_pfx, (uint32_t*)t.d_bits, n_bits, seed, 7u);
+    if (e == hipSuccess) e = hipEventRecord(job->ev[1], s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventElapsedTime(&adopt_ms, job->ev[0],
+                                                 job->ev[1]);
+    if (e != hipSuccess) {
+        set_err("reader_compact_begin: %s", hipGetErrorString(e));
+        rc = e == hipErrorOutOfMemory ? DBEEL_ERR_OOM : DBEEL_ERR_HIP;
+        goto fail;
+    }
+
+    /* host copies: what the caller writes to .compact_data/_index/_bloom */
+    if (out || (bloom_bytes && n_bits)) {
+        (void)hipEventRecord(job->ev[2], s);
+        if (out) {
+            rc = dbeel_gpu_job_fetch(job, out);
+            if (rc) goto fail;
+            d2h_bytes += out->data_len + out->index_len;
+        }
+        if (bloom_bytes && n_bits) {
+            /* "DBLM" | ver | k | pad | n_bits | seed | bitmap — the bytes
+             * dbeel_gpu_job_bloom returns for the same output */
+            const uint64_t blen = 32 + (n_bits + 7) / 8;
+            bbuf = (uint8_t*)calloc(1, blen + 4);
+            if (!bbuf) {
+                set_err("host alloc failed");
+                rc = DBEEL_ERR_OOM;
+                goto fail;
+            }
+            const uint32_t ver = 1, kk = 7, pad = 0;
+            memcpy(bbuf, "DBLM", 4);
+            memcpy(bbuf + 4, &ver, 4);
+            memcpy(bbuf + 8, &kk, 4);
+            memcpy(bbuf + 12, &pad, 4);
+            memcpy(bbuf + 16, &n_bits, 8);
+            memcpy(bbuf + 24, &seed, 8);
+            e = hipMemcpyAsync(bbuf + 32, t.d_bits, (n_bits + 7) / 8,
+                               hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            if (e != hipSuccess) {
+                set_err("filter D2H failed: %s", hipGetErrorString(e));
+                rc = DBEEL_ERR_HIP;
+                goto fail;
+            }
+            d2h_bytes += (n_bits + 7) / 8;
+            *bloom_bytes = bbuf;
+            *bloom_len = blen;
+            bbuf = nullptr;
+        }
+        (void)hipEventRecord(job->ev[3], s);
+        (void)hipEventSynchronize(job->ev[3]);
+        (void)hipEventElapsedTime(&d2h_ms, job->ev[2], job->ev[3]);
+    }
+    if (stats) {
+        stats->pipeline = pt;
+        stats->adopt_ms = adopt_ms;
+        stats->d2h_ms = d2h_ms;
+        stats->d2h_bytes = d2h_bytes;
+        stats->entries_in = job->total_entries;
+        stats->entries_out = out_entries;
+        stats->data_bytes_out = out_data_len;
+    }
+    dbeel_gpu_job_destroy(job);
+    rd->pending = t;
+    rd->pending_pos.assign(positions, positions + n_positions);
+    rd->has_pending = true;
+    return DBEEL_OK;
+
+fail:
+    (void)hipStreamSynchronize(s);
+    dbeel_gpu_job_destroy(job);
+    table_free(t);
+    free(bbuf);
+    if (out) dbeel_gpu_result_free(out);
+    if (bloom_bytes && *bloom_bytes) {
+        free(*bloom_bytes);
+        *bloom_bytes = nullptr;
+        *bloom_len = 0;
+    }
+    if (stats) memset(stats, 0, sizeof *stats);
+    return rc;
+}
+
+extern "C" int dbeel_gpu_reader_compact_commit(dbeel_gpu_reader* rd,
+                                               size_t out_pos) {
+    g_err[0] = 0;
+    if (!rd || !rd->has_pending) {
+        set_err("reader_compact_commit: no compaction pending");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    const size_t n_left = rd->tables.size() - rd->pending_pos.size();
+    if (out_pos > n_left) {
+        set_err("reader_compact_commit: out_pos %zu past the %zu runs left",
+                out_pos, n_left);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    HIP_CHECK(hipSetDevice(rd->device));
+    /* one list edit: partition out the inputs, place the output */
+    std::vector<ReaderTable> keep, gone;
+    keep.reserve(MAX_RUNS);
+    size_t k = 0;
+    for (size_t r = 0; r < rd->tables.size(); r++) {
+        if (k < rd->pending_pos.size() && rd->pending_pos[k] == r) {
+            gone.push_back(rd->tables[r]);
+            k++;
+        } else {
+            keep.push_back(rd->tables[r]);
+        }
+    }
+    keep.insert(keep.begin() + out_pos, rd->pending);
+    rd->tables.swap(keep);
+    rd->pending = ReaderTable();
+    rd->pending_pos.clear();
+    rd->has_pending = false;
+    /* reader_link leaves the stream idle: nothing reads the old tables */
+    hipError_t e = reader_link(rd);
+    for (ReaderTable& t : gone) table_free(t);
+    HIP_CHECK(e);
     return DBEEL_OK;
 }
 
@@ -2925,7 +3378,7 @@ extern "C" int dbeel_gpu_reader_get(dbeel_gpu_reader* rd,
     GET_CHECK(hipMemsetAsync(d_hits + n, 0, sizeof(dbeel_lookup_hit), s));
     GET_CHECK(hipEventRecord(rd->ev[1], s));
     hipLaunchKernelGGL(k_reader_search, dim3(pick_grid(n, READER_BLOCK)),
-                       dim3(READER_BLOCK), 0, s, rd->desc, rd->d_pfx,
+                       dim3(READER_BLOCK), 0, s, rd->desc, rd->pfx,
                        rd->d_blooms, rd->d_keys, d_koff, n, d_hits,
                        rd->d_stats);
     GET_CHECK(hipEventRecord(rd->ev[2], s));

@@ -265,6 +265,83 @@ extern "C" int dbeel_lsm_replay(const char* dir_c, uint32_t* out_replayed) {
     return DBEEL_OK;
 }
 
+namespace {
+
+/* The file half of a compaction (lsm_tree.rs:1070-1153), shared by
+ * dbeel_lsm_compact and dbeel_lsm_reader_compact: staging files, journal,
+ * crash hook, renames, [swap], deletes, journal removal. bloom == NULL
+ * writes no .compact_bloom. swap (may be NULL) runs between the renames
+ * and the deletes — where the reference swaps its sstable list
+ * (lsm_tree.rs:1113-1145); a failing swap stops there with its code,
+ * leaving the journal for dbeel_lsm_replay. *crashed (may be NULL) is set
+ * when DBEEL_LSM_CRASH_AFTER_JOURNAL stopped the sequence (rc is OK). */
+int compact_file_half(const std::string& dir, const uint64_t* indices,
+                      size_t n_indices, uint64_t output_index,
+                      const dbeel_compact_result& res, const uint8_t* bloom,
+                      uint64_t bloom_len, int (*swap)(void*), void* swap_arg,
+                      bool* crashed = nullptr) {
+    if (crashed) *crashed = false;
+    std::string cd = file_path(dir, output_index, "compact_data");
+    std::string ci = file_path(dir, output_index, "compact_index");
+    std::string cb = file_path(dir, output_index, "compact_bloom");
+    bool ok = write_whole(cd, res.data, res.data_len) &&
+              write_whole(ci, res.index, res.index_len);
+    if (ok && bloom) ok = write_whole(cb, bloom, bloom_len);
+    if (!ok) return DBEEL_ERR_IO;
+
+    /* journal (CompactionAction, lsm_tree.rs:1090-1105): renames of all
+     * three staging files, deletes of every input's data/index/bloom */
+    std::vector<uint8_t> journal;
+    put_u64(journal, 3); /* renames */
+    put_str(journal, cd);
+    put_str(journal, file_path(dir, output_index, "data"));
+    put_str(journal, ci);
+    put_str(journal, file_path(dir, output_index, "index"));
+    put_str(journal, cb);
+    put_str(journal, file_path(dir, output_index, "bloom"));
+    put_u64(journal, n_indices * 3); /* deletes */
+    std::vector<std::string> deletes;
+    for (size_t i = 0; i < n_indices; i++) {
+        deletes.push_back(file_path(dir, indices[i], "data"));
+        deletes.push_back(file_path(dir, indices[i], "index"));
+        deletes.push_back(file_path(dir, indices[i], "bloom"));
+    }
+    for (auto& d : deletes) put_str(journal, d);
+    std::string jpath = file_path(dir, output_index, "compact_action");
+    if (!write_whole(jpath, journal.data(), journal.size()))
+        return DBEEL_ERR_IO;
+
+    /* crash-injection hook for recovery tests (the flow_events analogue,
+     * reference flow_events.rs:7-14): stop after the journal is durable —
+     * dbeel_lsm_replay must complete the compaction idempotently */
+    if (getenv("DBEEL_LSM_CRASH_AFTER_JOURNAL")) {
+        if (crashed) *crashed = true;
+        return DBEEL_OK;
+    }
+
+    /* renames (source may be absent — no bloom), then deletes, then the
+     * journal itself (lsm_tree.rs:1107-1153) */
+    struct {
+        std::string from, to;
+    } renames[3] = {{cd, file_path(dir, output_index, "data")},
+                    {ci, file_path(dir, output_index, "index")},
+                    {cb, file_path(dir, output_index, "bloom")}};
+    for (auto& rn : renames)
+        if (exists(rn.from))
+            if (rename(rn.from.c_str(), rn.to.c_str()) != 0)
+                return DBEEL_ERR_IO;
+    if (swap) {
+        int rc = swap(swap_arg);
+        if (rc != DBEEL_OK) return rc;
+    }
+    for (auto& d : deletes)
+        if (exists(d)) unlink(d.c_str());
+    unlink(jpath.c_str());
+    return DBEEL_OK;
+}
+
+} // namespace
+
 extern "C" int dbeel_lsm_compact(const char* dir_c, const uint64_t* indices,
                                  size_t n_indices, uint64_t output_index,
                                  int keep_tombstones, int device,
@@ -309,64 +386,14 @@ extern "C" int dbeel_lsm_compact(const char* dir_c, const uint64_t* indices,
         return rc;
     }
 
-    std::string cd = file_path(dir, output_index, "compact_data");
-    std::string ci = file_path(dir, output_index, "compact_index");
-    std::string cb = file_path(dir, output_index, "compact_bloom");
-    bool ok = write_whole(cd, res.data, res.data_len) &&
-              write_whole(ci, res.index, res.index_len);
-    if (ok && with_bloom) ok = write_whole(cb, bloom, bloom_len);
-    uint64_t written = res.entries_written;
+    rc = compact_file_half(dir, indices, n_indices, output_index, res,
+                           with_bloom ? bloom : nullptr, bloom_len, nullptr,
+                           nullptr);
+    if (rc == DBEEL_OK && out_entries_written)
+        *out_entries_written = res.entries_written;
     dbeel_gpu_result_free(&res);
     dbeel_gpu_bloom_free(bloom);
-    if (!ok) return DBEEL_ERR_IO;
-
-    /* journal (CompactionAction, lsm_tree.rs:1090-1105): renames of all
-     * three staging files, deletes of every input's data/index/bloom */
-    std::vector<uint8_t> journal;
-    put_u64(journal, 3); /* renames */
-    put_str(journal, cd);
-    put_str(journal, file_path(dir, output_index, "data"));
-    put_str(journal, ci);
-    put_str(journal, file_path(dir, output_index, "index"));
-    put_str(journal, cb);
-    put_str(journal, file_path(dir, output_index, "bloom"));
-    put_u64(journal, n_indices * 3); /* deletes */
-    std::vector<std::string> deletes;
-    for (size_t i = 0; i < n_indices; i++) {
-        deletes.push_back(file_path(dir, indices[i], "data"));
-        deletes.push_back(file_path(dir, indices[i], "index"));
-        deletes.push_back(file_path(dir, indices[i], "bloom"));
-    }
-    for (auto& d : deletes) put_str(journal, d);
-    std::string jpath = file_path(dir, output_index, "compact_action");
-    if (!write_whole(jpath, journal.data(), journal.size()))
-        return DBEEL_ERR_IO;
-
-    /* crash-injection hook for recovery tests (the flow_events analogue,
-     * reference flow_events.rs:7-14): stop after the journal is durable —
-     * dbeel_lsm_replay must complete the compaction idempotently */
-    if (getenv("DBEEL_LSM_CRASH_AFTER_JOURNAL")) {
-        if (out_entries_written) *out_entries_written = written;
-        return DBEEL_OK;
-    }
-
-    /* renames (source may be absent — no bloom), then deletes, then the
-     * journal itself (lsm_tree.rs:1107-1153) */
-    struct {
-        std::string from, to;
-    } renames[3] = {{cd, file_path(dir, output_index, "data")},
-                    {ci, file_path(dir, output_index, "index")},
-                    {cb, file_path(dir, output_index, "bloom")}};
-    for (auto& rn : renames)
-        if (exists(rn.from))
-            if (rename(rn.from.c_str(), rn.to.c_str()) != 0)
-                return DBEEL_ERR_IO;
-    for (auto& d : deletes)
-        if (exists(d)) unlink(d.c_str());
-    unlink(jpath.c_str());
-
-    if (out_entries_written) *out_entries_written = written;
-    return DBEEL_OK;
+    return rc;
 }
 
 extern "C" int dbeel_lsm_major_compact(const char* dir_c, int device,
@@ -494,5 +521,143 @@ extern "C" int dbeel_lsm_compact_tree(const char* dir_c,
         done++;
     }
     if (out_n_compactions) *out_n_compactions = done;
+    return DBEEL_OK;
+}
+
+/* ---- live reader over a directory (include/dbeel_lsm.h) ---- */
+
+/* defined in dbeel_gpu.hip (same library, not exported) */
+extern "C" uint64_t dbeel_reader_run_data_len(const dbeel_gpu_reader* rd,
+                                              size_t pos);
+
+extern "C" int dbeel_lsm_reader_add(const char* dir_c, dbeel_gpu_reader* rd,
+                                    uint64_t* indices, size_t* n,
+                                    uint64_t sstable_index) {
+    if (!dir_c || !rd || !indices || !n) {
+        dbeel_set_last_error("lsm_reader_add: null argument");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (*n != dbeel_gpu_reader_run_count(rd) || *n >= 64) {
+        dbeel_set_last_error("lsm_reader_add: indices do not describe the "
+                             "reader, or it already holds 64 runs");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    /* ascending-index position: what a fresh dbeel_lsm_reader_open of the
+     * directory would give this sstable */
+    size_t pos = std::lower_bound(indices, indices + *n, sstable_index) -
+                 indices;
+    if (pos < *n && indices[pos] == sstable_index) {
+        dbeel_set_last_error("lsm_reader_add: sstable already in the reader");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    std::string dir(dir_c);
+    std::vector<uint8_t> data, index, bloom;
+    if (!read_whole(file_path(dir, sstable_index, "data"), data) ||
+        !read_whole(file_path(dir, sstable_index, "index"), index)) {
+        dbeel_set_last_error("cannot read an sstable's data/index file");
+        return DBEEL_ERR_IO;
+    }
+    dbeel_run_view view = {data.data(), data.size(), index.data(),
+                           index.size()};
+    dbeel_bloom_view bview = {nullptr, 0};
+    std::string bp = file_path(dir, sstable_index, "bloom");
+    if (exists(bp)) {
+        if (!read_whole(bp, bloom)) {
+            dbeel_set_last_error("cannot read an sstable's bloom file");
+            return DBEEL_ERR_IO;
+        }
+        static const uint8_t none = 0;
+        bview = {bloom.empty() ? &none : bloom.data(), bloom.size()};
+    }
+    int rc = dbeel_gpu_reader_insert_run(rd, pos, &view, &bview);
+    if (rc != DBEEL_OK) return rc;
+    for (size_t i = *n; i > pos; i--) indices[i] = indices[i - 1];
+    indices[pos] = sstable_index;
+    *n += 1;
+    return DBEEL_OK;
+}
+
+namespace {
+struct CommitArg {
+    dbeel_gpu_reader* rd;
+    size_t out_pos;
+};
+int commit_swap(void* p) {
+    CommitArg* a = (CommitArg*)p;
+    return dbeel_gpu_reader_compact_commit(a->rd, a->out_pos);
+}
+} // namespace
+
+extern "C" int dbeel_lsm_reader_compact(
+    const char* dir_c, dbeel_gpu_reader* rd, uint64_t* indices, size_t* n,
+    const uint64_t* compact_indices, size_t n_compact, uint64_t output_index,
+    int keep_tombstones, uint64_t sstable_bloom_min_size,
+    uint64_t* out_entries_written) {
+    if (!dir_c || !rd || !indices || !n || !compact_indices ||
+        n_compact == 0) {
+        dbeel_set_last_error("lsm_reader_compact: null or empty argument");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (*n != dbeel_gpu_reader_run_count(rd)) {
+        dbeel_set_last_error("lsm_reader_compact: indices do not describe "
+                             "the reader");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    /* sstable indices -> list positions; ascending index = ascending
+     * position, the order the (timestamp, run) tie-break needs */
+    std::vector<uint64_t> group(compact_indices, compact_indices + n_compact);
+    std::sort(group.begin(), group.end());
+    std::vector<uint32_t> positions;
+    uint64_t total_input_data = 0;
+    for (size_t i = 0; i < n_compact; i++) {
+        const uint64_t* it = std::lower_bound(indices, indices + *n, group[i]);
+        if (it == indices + *n || *it != group[i] ||
+            (i && group[i] == group[i - 1])) {
+            dbeel_set_last_error("lsm_reader_compact: an sstable to compact "
+                                 "is not in the reader, or is named twice");
+            return DBEEL_ERR_INVALID_ARG;
+        }
+        positions.push_back((uint32_t)(it - indices));
+        total_input_data += dbeel_reader_run_data_len(rd, it - indices);
+    }
+    /* the list after the swap, and where the output lands in it */
+    std::vector<uint64_t> after;
+    for (size_t i = 0; i < *n; i++)
+        if (!std::binary_search(group.begin(), group.end(), indices[i]))
+            after.push_back(indices[i]);
+    size_t out_pos = std::lower_bound(after.begin(), after.end(),
+                                      output_index) - after.begin();
+    if (out_pos < after.size() && after[out_pos] == output_index) {
+        dbeel_set_last_error("lsm_reader_compact: output index is a live "
+                             "sstable outside the compacted group");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    after.insert(after.begin() + out_pos, output_index);
+
+    /* same gate as dbeel_lsm_compact (lsm_tree.rs:1026-1034) */
+    bool with_bloom = total_input_data > sstable_bloom_min_size;
+    dbeel_compact_result res{};
+    uint8_t* bloom = nullptr;
+    uint64_t bloom_len = 0;
+    int rc = dbeel_gpu_reader_compact_begin(
+        rd, positions.data(), positions.size(), keep_tombstones,
+        with_bloom ? 1 : 0, &res, &bloom, &bloom_len, nullptr);
+    if (rc != DBEEL_OK) return rc;
+
+    CommitArg arg = {rd, out_pos};
+    bool crashed = false;
+    rc = compact_file_half(std::string(dir_c), group.data(), group.size(),
+                           output_index, res, with_bloom ? bloom : nullptr,
+                           bloom_len, commit_swap, &arg, &crashed);
+    uint64_t written = res.entries_written;
+    dbeel_gpu_result_free(&res);
+    dbeel_gpu_bloom_free(bloom);
+    /* not committed (failure before the swap, or the crash hook): the
+     * reader keeps answering from the old list */
+    dbeel_gpu_reader_compact_abort(rd);
+    if (out_entries_written && rc == DBEEL_OK) *out_entries_written = written;
+    if (rc != DBEEL_OK || crashed) return rc;
+    for (size_t i = 0; i < after.size(); i++) indices[i] = after[i];
+    *n = after.size();
     return DBEEL_OK;
 }

@@ -423,6 +423,23 @@ class GetStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ReaderCompactStats(ctypes.Structure):
+    _fields_ = [
+        ("pipeline", CompactTimings),
+        ("adopt_ms", ctypes.c_double),
+        ("d2h_ms", ctypes.c_double),
+        ("d2h_bytes", ctypes.c_uint64),
+        ("entries_in", ctypes.c_uint64),
+        ("entries_out", ctypes.c_uint64),
+        ("data_bytes_out", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_[1:]}
+        d["pipeline"] = self.pipeline.as_dict()
+        return d
+
+
 def _load_reader() -> ctypes.CDLL:
     lib = load()
     if not hasattr(lib, "_reader_ready"):
@@ -443,6 +460,29 @@ def _load_reader() -> ctypes.CDLL:
         lib.dbeel_gpu_get_result_free.argtypes = [ctypes.POINTER(GetResult)]
         lib.dbeel_gpu_reader_close.restype = None
         lib.dbeel_gpu_reader_close.argtypes = [ctypes.c_void_p]
+        lib.dbeel_gpu_reader_run_count.restype = ctypes.c_size_t
+        lib.dbeel_gpu_reader_run_count.argtypes = [ctypes.c_void_p]
+        lib.dbeel_gpu_reader_insert_run.restype = ctypes.c_int
+        lib.dbeel_gpu_reader_insert_run.argtypes = [
+            ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(RunView),
+            ctypes.POINTER(BloomView),
+        ]
+        lib.dbeel_gpu_reader_compact_begin.restype = ctypes.c_int
+        lib.dbeel_gpu_reader_compact_begin.argtypes = [
+            ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
+            ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
+            ctypes.POINTER(CompactResult),
+            ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)),
+            ctypes.POINTER(ctypes.c_uint64),
+            ctypes.POINTER(ReaderCompactStats),
+        ]
+        lib.dbeel_gpu_reader_compact_commit.restype = ctypes.c_int
+        lib.dbeel_gpu_reader_compact_commit.argtypes = [
+            ctypes.c_void_p, ctypes.c_size_t]
+        lib.dbeel_gpu_reader_compact_abort.restype = None
+        lib.dbeel_gpu_reader_compact_abort.argtypes = [ctypes.c_void_p]
+        lib.dbeel_gpu_bloom_free.restype = None
+        lib.dbeel_gpu_bloom_free.argtypes = [ctypes.POINTER(ctypes.c_uint8)]
         lib._reader_ready = True
     return lib
 
@@ -452,7 +492,13 @@ class Reader:
     lsm_tree.rs:674-723): runs [(data, index), ...] and their optional
     "DBLM" filters (blooms[r] = the .bloom file's bytes, or None) are
     uploaded once; every get() after that moves only keys in and hits +
-    packed values out. No host copy of the runs is needed afterwards."""
+    packed values out. No host copy of the runs is needed afterwards.
+
+    The reader is live: insert_run() takes a flushed run, compact_begin()
+    / compact_commit() compact runs it already holds in HBM and swap the
+    list in one step (the reference's shared sstable list,
+    lsm_tree.rs:901-915 and 1113-1145). Runs are named by position in the
+    list, which is what hit["run"] reports."""
 
     def __init__(self, runs, blooms=None, device: int = 0):
         self._lib = _load_reader()
@@ -489,8 +535,94 @@ class Reader:
 
     @property
     def table_bytes(self) -> int:
-        """Device bytes held between calls: slab + prefixes + bitmaps."""
+        """Device bytes held between calls, summed over the tables: run
+        bytes + prefixes + bitmaps."""
         return int(self._lib.dbeel_gpu_reader_table_bytes(self._h))
+
+    @property
+    def n_runs(self) -> int:
+        return int(self._lib.dbeel_gpu_reader_run_count(self._h))
+
+    def _check(self, rc):
+        if rc != 0:
+            raise DbeelGpuError(rc, self._lib.dbeel_gpu_last_error().decode())
+
+    def insert_run(self, pos: int, run, bloom=None):
+        """Flush: upload one run (data, index) and its optional "DBLM"
+        filter bytes, inserted at position pos in [0, n_runs]; runs at
+        >= pos move up by one. On failure the reader is unchanged."""
+        if not self._h:
+            raise ValueError("reader is closed")
+        views, keepalive = _views([run])
+        bview = None
+        if bloom is not None:
+            a = np.frombuffer(bytes(bloom) or b"\0", dtype=np.uint8)
+            keepalive.append(a)
+            bview = BloomView(
+                a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), len(bloom))
+        self._check(self._lib.dbeel_gpu_reader_insert_run(
+            self._h, pos, views, None if bview is None else ctypes.byref(bview)))
+        del keepalive
+
+    def compact_begin(self, positions, keep_tombstones: bool,
+                      bloom: bool = False, fetch: bool = True):
+        """Compact the runs at `positions` (strictly ascending) where they
+        lie in HBM. The output becomes a pending table: gets keep seeing
+        the old list until compact_commit(). Returns (data, index,
+        bloom_bytes, stats): the output run's file bytes (None, None when
+        fetch=False), its "DBLM" filter bytes (None unless bloom) and the
+        stats dict."""
+        if not self._h:
+            raise ValueError("reader is closed")
+        positions = list(positions)
+        pos = (ctypes.c_uint32 * max(1, len(positions)))(*positions)
+        res = CompactResult()
+        st = ReaderCompactStats()
+        bp = ctypes.POINTER(ctypes.c_uint8)()
+        bn = ctypes.c_uint64()
+        want_bloom = bool(bloom) and fetch
+        rc = self._lib.dbeel_gpu_reader_compact_begin(
+            self._h, pos, len(positions), int(keep_tombstones), int(bloom),
+            ctypes.byref(res) if fetch else None,
+            ctypes.byref(bp) if want_bloom else None,
+            ctypes.byref(bn) if want_bloom else None, ctypes.byref(st))
+        self._check(rc)
+        data = index = bloom_bytes = None
+        try:
+            if fetch:
+                data = _ptr_bytes(res.data, res.data_len)
+                index = _ptr_bytes(res.index, res.index_len)
+            if want_bloom:
+                bloom_bytes = _ptr_bytes(bp, int(bn.value))
+        finally:
+            if fetch:
+                self._lib.dbeel_gpu_result_free(ctypes.byref(res))
+            if want_bloom:
+                self._lib.dbeel_gpu_bloom_free(bp)
+        return data, index, bloom_bytes, st.as_dict()
+
+    def compact_commit(self, out_pos: int):
+        """Swap: remove the compacted runs, insert the pending output at
+        out_pos in [0, n_runs - len(positions)]."""
+        self._check(self._lib.dbeel_gpu_reader_compact_commit(self._h,
+                                                              out_pos))
+
+    def compact_abort(self):
+        """Drop the pending output; the list is unchanged."""
+        if self._h:
+            self._lib.dbeel_gpu_reader_compact_abort(self._h)
+
+    def compact(self, positions, out_pos: int, keep_tombstones: bool,
+                bloom: bool = False, fetch: bool = True):
+        """compact_begin followed by compact_commit."""
+        out = self.compact_begin(positions, keep_tombstones, bloom=bloom,
+                                 fetch=fetch)
+        try:
+            self.compact_commit(out_pos)
+        except DbeelGpuError:
+            self.compact_abort()
+            raise
+        return out
 
     def get_raw(self, keys):
         """-> (hits HIT_DTYPE array, value_offsets u64[n+1], values u8

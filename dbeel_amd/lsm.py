@@ -138,6 +138,68 @@ def open_reader(dir: str, device: int = 0):
     return Reader._from_handle(h), [int(idx[i]) for i in range(n.value)]
 
 
+def _load_live(lib):
+    if not hasattr(lib, "_lsm_live_ready"):
+        lib.dbeel_lsm_reader_add.restype = ctypes.c_int
+        lib.dbeel_lsm_reader_add.argtypes = [
+            ctypes.c_char_p, ctypes.c_void_p,
+            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_size_t),
+            ctypes.c_uint64,
+        ]
+        lib.dbeel_lsm_reader_compact.restype = ctypes.c_int
+        lib.dbeel_lsm_reader_compact.argtypes = [
+            ctypes.c_char_p, ctypes.c_void_p,
+            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_size_t),
+            ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t,
+            ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64,
+            ctypes.POINTER(ctypes.c_uint64),
+        ]
+        lib._lsm_live_ready = True
+    return lib
+
+
+def _indices_array(indices):
+    if len(indices) > 64:
+        raise ValueError("a reader holds at most 64 sstables")
+    return ((ctypes.c_uint64 * 64)(*indices),
+            ctypes.c_size_t(len(indices)))
+
+
+def reader_add(dir: str, reader, indices, sstable_index: int):
+    """A flush wrote sstable_index: read its files and insert the run into
+    the open reader at its ascending-index position. Returns the new
+    indices list; the reader then answers as a fresh open_reader(dir)
+    would."""
+    lib = _load_live(load())
+    idx, n = _indices_array(indices)
+    rc = lib.dbeel_lsm_reader_add(dir.encode(), reader._h, idx,
+                                  ctypes.byref(n), sstable_index)
+    _check(rc, lib)
+    return [int(idx[i]) for i in range(n.value)]
+
+
+def reader_compact(dir: str, reader, indices, compact_indices,
+                   output_index: int, keep_tombstones: bool,
+                   device_unused=None,
+                   bloom_min_size: int = DEFAULT_BLOOM_MIN_SIZE):
+    """compact() for a directory an open reader covers: the runs are
+    compacted where they lie in the reader's device memory (no file reads,
+    no upload), the directory goes through the same staging / journal /
+    rename / delete sequence, and the reader's list is swapped between the
+    renames and the deletes. Returns the new indices list. The device is
+    the reader's; device_unused keeps compact()'s argument order."""
+    lib = _load_live(load())
+    idx, n = _indices_array(indices)
+    arr = (ctypes.c_uint64 * max(1, len(compact_indices)))(*compact_indices)
+    out = ctypes.c_uint64()
+    rc = lib.dbeel_lsm_reader_compact(
+        dir.encode(), reader._h, idx, ctypes.byref(n), arr,
+        len(compact_indices), output_index, int(keep_tombstones),
+        bloom_min_size, ctypes.byref(out))
+    _check(rc, lib)
+    return [int(idx[i]) for i in range(n.value)]
+
+
 def write_run_files(dir: str, index: int, data: bytes, idx: bytes) -> None:
     """Write {index:020}.data/.index (test/bench helper)."""
     os.makedirs(dir, exist_ok=True)

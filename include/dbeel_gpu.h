@@ -161,8 +161,9 @@ int dbeel_gpu_lookup(const dbeel_run_view* runs, size_t n_runs,
  * strictly ascending by key and builds the dense 8-byte key-prefix array
  * the search runs on; any violation is DBEEL_ERR_CORRUPT.
  *
- * A reader holds the padded run slab, 8 B per entry of prefixes, the
- * filter bitmaps (dbeel_gpu_reader_table_bytes reports their sum) and
+ * A reader holds one table per run — the padded run bytes, 8 B per entry
+ * of prefixes, the filter bitmap (dbeel_gpu_reader_table_bytes reports the
+ * sum over its tables, a pending compaction output included) — and
  * per-batch scratch that grows on demand and is reused — no compaction
  * buffers. One thread at a time per reader; distinct readers are
  * independent. */
@@ -207,7 +208,70 @@ int dbeel_gpu_reader_get(dbeel_gpu_reader* reader, const uint8_t* keys,
                          dbeel_get_result* out,
                          dbeel_get_stats* stats /* may be NULL */);
 void dbeel_gpu_get_result_free(dbeel_get_result* r);
+/* Frees the reader; a pending compaction is aborted. */
 void dbeel_gpu_reader_close(dbeel_gpu_reader* reader);
+
+/* ---- Live reader: the shared sstable list ----
+ * The reference's LSMTree keeps one list of open sstables that reads,
+ * flushes and compactions share: a flush pushes the new table
+ * (lsm_tree.rs:901-915); a compaction partitions out its inputs, pushes
+ * the output, sorts and swaps the list while reads in flight finish on the
+ * old one (lsm_tree.rs:1113-1145). The reader holds one device table per
+ * run (run bytes padded like a job's input, 8 B per entry of prefixes, an
+ * optional filter bitmap), so the list can take a flushed run, compact
+ * runs it already holds without moving them, and swap in one step. Runs
+ * are identified by position in the list — what hit.run reports. Same
+ * contract as above: one thread at a time per reader. */
+size_t dbeel_gpu_reader_run_count(const dbeel_gpu_reader* reader);
+
+/* Flush: upload ONE run (and its filter, may be NULL) and insert it at
+ * position pos in [0, n_runs]; runs at >= pos move up by one. Arguments
+ * are validated on the host before any device call (NULL reader/run,
+ * pos > n_runs or a reader already at 64 runs: DBEEL_ERR_INVALID_ARG; a
+ * bad filter header: DBEEL_ERR_CORRUPT), then the run is uploaded and
+ * checked by the open-time device pass, then linked in. On any failure the
+ * reader is exactly as it was (same answers, same table_bytes). */
+int dbeel_gpu_reader_insert_run(dbeel_gpu_reader* reader, size_t pos,
+                                const dbeel_run_view* run,
+                                const dbeel_bloom_view* bloom);
+
+/* Compaction of runs the reader already holds, with no input H2D. */
+typedef struct {
+    dbeel_compact_timings pipeline; /* h2d_ms = 0 by construction        */
+    double   adopt_ms;   /* output -> resident table: D2D copy + k_reader_adopt */
+    double   d2h_ms;     /* fetch of out / filter bytes, 0 when not asked */
+    uint64_t d2h_bytes;
+    uint64_t entries_in, entries_out, data_bytes_out;
+} dbeel_reader_compact_stats;
+
+/* begin: runs the compaction pipeline over the tables at positions[]
+ * (strictly ascending, in range, at least one; n_positions == 1 rewrites
+ * one run) in place, copies the output device-to-device into a new
+ * right-sized table, builds its prefix array and — when build_bloom — its
+ * filter (dbeel_gpu_job_bloom's parameters) in one device pass, and holds
+ * that table PENDING: gets keep being answered from the old list until
+ * commit. out (NULL = leave the bytes on the device) and bloom_bytes /
+ * bloom_len (both NULL, or both set; filled when build_bloom, free with
+ * dbeel_gpu_bloom_free) receive exactly the bytes dbeel_gpu_compact and
+ * dbeel_gpu_job_bloom give for the same runs. At most one compaction may
+ * be pending (a second begin is DBEEL_ERR_INVALID_ARG). On failure
+ * (including DBEEL_ERR_OOM) the reader is untouched.
+ *
+ * commit: removes the input tables and inserts the pending one at out_pos
+ * in [0, n_runs - n_positions] — one host-side list edit and a descriptor
+ * upload; an empty output stays in the list as an empty run. Nothing
+ * pending, or a bad out_pos (the pending table survives it), is
+ * DBEEL_ERR_INVALID_ARG.
+ *
+ * abort: frees the pending table; no-op when nothing is pending. */
+int dbeel_gpu_reader_compact_begin(dbeel_gpu_reader* reader,
+        const uint32_t* positions, size_t n_positions,
+        int keep_tombstones, int build_bloom,
+        dbeel_compact_result* out,
+        uint8_t** bloom_bytes, uint64_t* bloom_len,
+        dbeel_reader_compact_stats* stats /* may be NULL */);
+int  dbeel_gpu_reader_compact_commit(dbeel_gpu_reader* reader, size_t out_pos);
+void dbeel_gpu_reader_compact_abort(dbeel_gpu_reader* reader);
 
 /* ---- Run encoder (the memtable-flush path) ----
  * Encodes an already-sorted (key, value, timestamp) stream into a run:

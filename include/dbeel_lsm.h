@@ -90,6 +90,42 @@ int dbeel_lsm_reader_open(const char* dir, int device,
                           struct dbeel_gpu_reader** out,
                           uint64_t* out_indices, size_t* out_n);
 
+/* Keep an open reader in step with its directory instead of reopening it.
+ * indices[] is the caller's array from dbeel_lsm_reader_open (capacity
+ * 64), *n its length; both are updated on success and left alone on
+ * failure. After either call the reader answers exactly as a fresh
+ * dbeel_lsm_reader_open of the directory would.
+ *
+ * reader_add: a flush wrote sstable_index (lsm_tree.rs:901-915). Reads
+ * {i:020}.data/.index (+ .bloom if present) and inserts the run at its
+ * ascending-index position; an index already present is
+ * DBEEL_ERR_INVALID_ARG. (The reference appends a flushed table to the end
+ * of its list and sorts only at the next compaction or restart,
+ * lsm_tree.rs:903-912,1136 — documented divergence)
+ *
+ * reader_compact: dbeel_lsm_compact with the read-and-upload half replaced
+ * by a compaction of the runs the reader already holds
+ * (lsm_tree.rs:1113-1145): compact on the device -> staging files ->
+ * journal -> renames -> swap the reader's list -> delete inputs -> remove
+ * the journal. The directory ends byte-for-byte as dbeel_lsm_compact
+ * leaves it; the bloom gate compares the compacted runs' data bytes with
+ * sstable_bloom_min_size. A compact_indices entry not in indices, or an
+ * output_index that is live and not itself compacted, is
+ * DBEEL_ERR_INVALID_ARG. Any failure before the swap leaves the reader
+ * answering from the old list. With DBEEL_LSM_CRASH_AFTER_JOURNAL set it
+ * stops after the journal as dbeel_lsm_compact does (reader and indices
+ * unchanged): the directory then needs dbeel_lsm_replay and the reader a
+ * reopen. */
+int dbeel_lsm_reader_add(const char* dir, struct dbeel_gpu_reader* reader,
+                         uint64_t* indices, size_t* n,
+                         uint64_t sstable_index);
+int dbeel_lsm_reader_compact(const char* dir, struct dbeel_gpu_reader* reader,
+                             uint64_t* indices, size_t* n,
+                             const uint64_t* compact_indices, size_t n_compact,
+                             uint64_t output_index, int keep_tombstones,
+                             uint64_t sstable_bloom_min_size,
+                             uint64_t* out_entries_written);
+
 #ifdef __cplusplus
 }
 #endif

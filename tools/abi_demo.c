@@ -2,9 +2,10 @@
  *
  * Proves the drop-in boundary is host-language-free: this file compiles
  * with gcc (no hipcc, no C++), links only libdbeel_gpu.so, and performs a
- * compaction + a lookup + a scan through exactly the declarations of
- * include/dbeel_gpu.h — the same calls dbeel's Rust FFI stub
- *  would make through cgo/bindgen.
+ * compaction + a lookup + a scan + a live-reader insert/compact/swap
+ * through exactly the declarations of include/dbeel_gpu.h — the same
+ * calls dbeel's Rust FFI stub would make through
+ * cgo/bindgen.
  *
  * Build (tests/test_abi.py does this on CPU; a GPU test runs it):
  *   gcc -O2 -I include tools/abi_demo.c -L dbeel_amd -ldbeel_gpu \
@@ -120,7 +121,51 @@ int main(void) {
     }
     dbeel_gpu_result_free(&res);
 
-    printf("abi_demo OK: compact(3 survivors, b=NEW) + lookup + scan "
-           "through the plain-C ABI\n");
+    /* live reader: open over run 0, take run 1 as a flushed run, compact
+     * both where they lie on the device, swap the list, read "b" back */
+    {
+        dbeel_gpu_reader* rd = NULL;
+        dbeel_reader_compact_stats cst;
+        dbeel_get_result got;
+        uint32_t pos[2] = {0, 1};
+        rc = dbeel_gpu_reader_open(runs, NULL, 1, 0, &rd);
+        if (rc == DBEEL_OK) rc = dbeel_gpu_reader_insert_run(rd, 1, &runs[1],
+                                                             NULL);
+        if (rc == DBEEL_OK)
+            rc = dbeel_gpu_reader_compact_begin(rd, pos, 2, 0, 0, &res, NULL,
+                                                NULL, &cst);
+        if (rc != DBEEL_OK) {
+            fprintf(stderr, "live reader rc=%d: %s\n", rc,
+                    dbeel_gpu_last_error());
+            dbeel_gpu_reader_close(rd);
+            return 1;
+        }
+        int bad = res.entries_written != 3 || cst.entries_in != 5 ||
+                  cst.pipeline.h2d_ms != 0.0 ||
+                  dbeel_gpu_reader_run_count(rd) != 2; /* still pending */
+        dbeel_gpu_result_free(&res);
+        rc = dbeel_gpu_reader_compact_commit(rd, 0);
+        if (rc == DBEEL_OK) rc = dbeel_gpu_reader_get(rd, keys, koff, 2, &got,
+                                                      NULL);
+        if (rc != DBEEL_OK) {
+            fprintf(stderr, "live reader rc=%d: %s\n", rc,
+                    dbeel_gpu_last_error());
+            dbeel_gpu_reader_close(rd);
+            return 1;
+        }
+        bad = bad || dbeel_gpu_reader_run_count(rd) != 1 ||
+              got.hits[0].run != 0 || got.values_len != 3 ||
+              memcmp(got.values, "NEW", 3) != 0 ||
+              got.hits[1].run != -1; /* the tombstone was dropped */
+        dbeel_gpu_get_result_free(&got);
+        dbeel_gpu_reader_close(rd);
+        if (bad) {
+            fprintf(stderr, "live reader results wrong\n");
+            return 2;
+        }
+    }
+
+    printf("abi_demo OK: compact(3 survivors, b=NEW) + lookup + scan + "
+           "live reader through the plain-C ABI\n");
     return 0;
 }

@@ -137,9 +137,15 @@ def reader_trial(rng, runs, device):
             queries.append(bytes(rng.integers(
                 0, 256, int(rng.integers(0, 40)), dtype=np.uint8)))
     exp = [model[k][1] if k in model else None for k in queries]
+    live_why = None
     with Reader(runs, blooms=blooms, device=device) as rd:
         got = rd.get(queries)
         _, _, _, st = rd.get_raw(queries)
+        if got == exp:
+            live_why = live_reader_step(rng, rd, runs, blooms, queries,
+                                        device)
+    if live_why:
+        return live_why
     if got != exp:
         bad = next(i for i, (g, e) in enumerate(zip(got, exp)) if g != e)
         return f"key {queries[bad].hex()} got {got[bad]} want {exp[bad]}"
@@ -155,6 +161,53 @@ def reader_trial(rng, runs, device):
             if not lsm.bloom_contains(blooms[r], e.key):
                 return f"filter of run {r} misses stored key {e.key.hex()}"
     return None
+
+
+def live_reader_step(rng, rd, runs, blooms, queries, device):
+    """One random insert and one random compaction applied to the open
+    reader, each compared field for field against a freshly opened reader
+    over the resulting list (the compaction's output from the oracle)."""
+    from dbeel_amd.engine import Reader
+
+    def differs(what):
+        with Reader(runs, blooms=blooms, device=device) as fresh:
+            got, want = rd.get_raw(queries), fresh.get_raw(queries)
+        for f in ("run", "is_tombstone", "value_offset", "value_len"):
+            if not np.array_equal(got[0][f], want[0][f]):
+                return f"after {what}: hit field {f} differs from a reopen"
+        if (not np.array_equal(got[1], want[1])
+                or got[2].tobytes() != want[2].tobytes()):
+            return f"after {what}: values differ from a reopen"
+        return None
+
+    runs, blooms = list(runs), list(blooms)
+    if len(runs) < 64:
+        new = random_runs(rng)[0]
+        pos = int(rng.integers(0, len(runs) + 1))
+        rd.insert_run(pos, new)
+        runs.insert(pos, new)
+        blooms.insert(pos, None)
+        why = differs(f"insert at {pos}")
+        if why:
+            return why
+    n = len(runs)
+    k = int(rng.integers(1, n + 1))
+    positions = sorted(int(p) for p in rng.choice(n, size=k, replace=False))
+    out_pos = int(rng.integers(0, n - k + 1))
+    keep = bool(rng.integers(0, 2))
+    with_bloom = bool(rng.integers(0, 2))
+    gd, gi, gb, _ = rd.compact(positions, out_pos, keep, bloom=with_bloom)
+    od, oi, _ = oracle.compact([runs[p] for p in positions],
+                               keep_tombstones=keep)
+    what = f"compact {positions} -> {out_pos} keep={keep}"
+    if (gd, gi) != (od, oi):
+        return f"{what}: output differs from the oracle"
+    chosen = set(positions)
+    runs = [r for p, r in enumerate(runs) if p not in chosen]
+    blooms = [b for p, b in enumerate(blooms) if p not in chosen]
+    runs.insert(out_pos, (od, oi))
+    blooms.insert(out_pos, gb)
+    return differs(what)
 
 
 def main():

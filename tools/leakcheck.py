@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Device-memory stability check: churn job create/run/fetch/destroy,
 streamed ingests (each creates ~per-chunk HIP events), batched jobs,
-scans, sliced compactions and resident readers (open / get x N / close),
-reporting hipMemGetInfo drift. A leak in
+scans, sliced compactions and resident readers (open / get x N / insert /
+compact begin + abort + commit / close), reporting hipMemGetInfo drift. A leak in
 any path shows as monotonically shrinking free memory.
 
     python tools/leakcheck.py --iters 40
@@ -91,6 +91,14 @@ def main():
                         device=0) as rd:
                 for n in (10, 4000, 100, 20_000):
                     rd.get(probe_keys[:n])
+                # live updates: insert / compact / abort / commit — every
+                # table they allocate is freed by the swap or by close
+                rd.insert_run(2, runs2[0])
+                rd.compact_begin([0, 2], True, bloom=True)
+                rd.compact_abort()
+                rd.compact([1, 3, 4], 0, False, bloom=True)
+                rd.compact_begin([0, 1], True, fetch=False)  # close aborts
+                rd.get(probe_keys[:4000])
             f = free_mem()
             if base is None:
                 base = f
