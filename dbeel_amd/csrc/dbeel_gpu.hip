@@ -14,9 +14,10 @@
  *                  merge runs on. Rangeable for streamed ingest.
  *   k_corank     : block-cooperative merge-path co-ranking — for every
  *                  run pair WITHIN a job, diagonal-partitioned
- *                  4096-position windows; blocks stage both prefix
+ *                  2048-position windows; blocks stage both prefix
  *                  segments into LDS coalesced and walk CORANK_STEPS
- *                  merged positions per thread, recording crossranks
+ *                  merged positions per thread (prefix-tied pairs are
+ *                  settled ahead of the walk), recording crossranks
  *                  (order = key bytes asc, timestamp i128 asc, run index
  *                  asc — lsm_tree.rs:52-71 + mod.rs:75-81) and
  *                  newest-wins supersession flags (lsm_tree.rs:1041-1044).
@@ -29,7 +30,8 @@
  *                  lookback fast path) -> survivor byte offsets +
  *                  positions.
  *   k_emit       : output .index records (offset/key_size/full_size,
- *                  entry_writer.rs:79-87) + compacted source map.
+ *                  entry_writer.rs:79-87) + compacted source map + the
+ *                  step totals record that winmap/copy read on-device.
  *   k_winmap/k_copy : verbatim survivor copy, balanced by DESTINATION
  *                  granule (16-B granules per lane, window/grid geometry
  *                  picked per survivor size from interleaved A/Bs, LDS
@@ -268,14 +270,16 @@ static_assert(sizeof(AuxT<40, true>) == 64, "tier-2 aux must be 64B");
  * is consistent: equality there with different klen means one key is a
  * zero-extension of the other within 8 bytes, which the klen comparison
  * below orders correctly (a strict prefix sorts first). */
+/* The record part of that compare: works on two aux records wherever they
+ * live (global memory, or registers a caller loaded ahead of need). Sets
+ * `deep` and returns 0 when both keys run past the staged 8+KB bytes and
+ * tie through them — only the blob can order those. */
 template <int KB, bool TS>
-__device__ __forceinline__ int cmp_keys_sfx(const RunsDesc& R,
-                                            const AuxT<KB, TS>* aux, int rA,
-                                            uint64_t iA, int rB,
-                                            uint64_t iB) {
-    const AuxT<KB, TS>* a = aux + R.entry_base[rA] + iA;
-    const AuxT<KB, TS>* b = aux + R.entry_base[rB] + iB;
-    uint32_t la = a->klen, lb = b->klen;
+__device__ __forceinline__ int cmp_keys_rec(const AuxT<KB, TS>& a,
+                                            const AuxT<KB, TS>& b,
+                                            bool& deep) {
+    deep = false;
+    uint32_t la = a.klen, lb = b.klen;
     uint32_t n = la < lb ? la : lb;
     uint32_t ns = n > 8 ? n - 8 : 0; /* suffix bytes to compare */
     if (ns > KB) ns = KB;
@@ -283,8 +287,8 @@ __device__ __forceinline__ int cmp_keys_sfx(const RunsDesc& R,
     for (uint32_t i = 0; i < KB; i += 8) {
         if (i >= ns) break;
         uint64_t va, vb;
-        __builtin_memcpy(&va, a->key + i, 8);
-        __builtin_memcpy(&vb, b->key + i, 8);
+        __builtin_memcpy(&va, a.key + i, 8);
+        __builtin_memcpy(&vb, b.key + i, 8);
         if (i + 8 > ns) { /* mask the tail; reading into klen is masked
                              off (and pad bytes are zero anyway) */
             uint64_t mask = (~0ull) >> (8 * (i + 8 - ns));
@@ -298,13 +302,29 @@ __device__ __forceinline__ int cmp_keys_sfx(const RunsDesc& R,
         }
     }
     if (la > (uint32_t)(8 + KB) && lb > (uint32_t)(8 + KB)) {
+        deep = true;
+        return 0;
+    }
+    return la < lb ? -1 : (la > lb ? 1 : 0);
+}
+
+template <int KB, bool TS>
+__device__ __forceinline__ int cmp_keys_sfx(const RunsDesc& R,
+                                            const AuxT<KB, TS>* aux, int rA,
+                                            uint64_t iA, int rB,
+                                            uint64_t iB) {
+    const AuxT<KB, TS>* a = aux + R.entry_base[rA] + iA;
+    const AuxT<KB, TS>* b = aux + R.entry_base[rB] + iB;
+    bool deep;
+    int c = cmp_keys_rec<KB, TS>(*a, *b, deep);
+    if (deep) {
         /* rare: long keys tied through the staged 8+KB bytes */
         EView ea, eb;
         if (!load_entry(R, rA, iA, ea) || !load_entry(R, rB, iB, eb))
             return -1; /* corrupt input flagged elsewhere; value discarded */
         return cmp_keys(ea.key, ea.klen, eb.key, eb.klen);
     }
-    return la < lb ? -1 : (la > lb ? 1 : 0);
+    return c;
 }
 
 /* (timestamp, run index) tie-break from the blob — only reached on fully
@@ -342,6 +362,78 @@ __device__ __forceinline__ int cmp_sfx_full(const RunsDesc& R,
     } else {
         return cmp_ts_run_blob(R, rA, iA, rB, iB);
     }
+}
+
+/* cmp_sfx_full that also reports whether the KEYS are equal, so a caller
+ * that needs both answers about one pair (who goes first; is the other a
+ * duplicate key) reads the pair's records once. Returns A < B. */
+template <int KB, bool TS>
+__device__ __forceinline__ bool tie_eval(const RunsDesc& R,
+                                         const AuxT<KB, TS>* aux, int rA,
+                                         uint64_t iA, int rB, uint64_t iB,
+                                         bool& keq) {
+    int c = cmp_keys_sfx<KB, TS>(R, aux, rA, iA, rB, iB);
+    keq = (c == 0);
+    if (c) return c < 0;
+    if constexpr (TS) {
+        const AuxT<KB, TS>* a = aux + R.entry_base[rA] + iA;
+        const AuxT<KB, TS>* b = aux + R.entry_base[rB] + iB;
+        if (a->ts_hi != b->ts_hi) return a->ts_hi < b->ts_hi;
+        if (a->ts_lo != b->ts_lo) return a->ts_lo < b->ts_lo;
+        return rA < rB;
+    } else {
+        return cmp_ts_run_blob(R, rA, iA, rB, iB) < 0;
+    }
+}
+
+/* Merge-path split on diagonal d: the smallest s in [lo, hi] for which
+ * A[s] < B[d-s-1] (full order) is false. pa(s) / pb(s) give the 8-byte
+ * prefixes, full_lt(s, t) the full compare of A[s] with B[t].
+ *
+ * The prefixes decide wherever they can. Q(s) = pa(s) < pb(d-s-1) implies
+ * the full predicate and is monotone like it, so a search on Q alone (ties
+ * counted false) lands at or before the true split, and the steps between
+ * the two are exactly the leading part of the stretch [s_Q, e) on which the
+ * two prefixes are equal (pa rises and pb(d-s-1) falls with s, so that
+ * stretch is contiguous and everything past it is "greater"). Full
+ * compares, the only ones that leave the prefix array, settle that stretch:
+ * one for a lone tied pair, a binary search otherwise. The result is the
+ * split a search on the full predicate finds. */
+template <typename T, typename PA, typename PB, typename FULL>
+__device__ __forceinline__ T diag_split(T lo, T hi, T d, PA pa, PB pb,
+                                        FULL full_lt) {
+    const T hi0 = hi;
+    while (lo < hi) {
+        T mid = (lo + hi) >> 1;
+        if (pa(mid) < pb(d - mid - 1))
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    if (lo < hi0 && pa(lo) == pb(d - lo - 1)) {
+        T e = lo + 1;
+        if (e < hi0 && pa(e) == pb(d - e - 1)) {
+            T l = e + 1, h = hi0; /* first s past the equal stretch */
+            while (l < h) {
+                T m = (l + h) >> 1;
+                if (pa(m) == pb(d - m - 1))
+                    l = m + 1;
+                else
+                    h = m;
+            }
+            e = l;
+        }
+        T l = lo, h = e;
+        while (l < h) {
+            T m = (l + h) >> 1;
+            if (full_lt(m, d - m - 1))
+                l = m + 1;
+            else
+                h = m;
+        }
+        lo = l;
+    }
+    return lo;
 }
 
 /* Validates every entry (bounds + bincode field cross-check,
@@ -442,7 +534,16 @@ __global__ void k_prepare(RunsDesc R, uint64_t g0, uint64_t g1,
 
 #define CORANK_BLOCK 256
 #define CORANK_STEPS 8
-#define CORANK_BLOCK_POS (CORANK_BLOCK * CORANK_STEPS) /* 4096 */
+#define CORANK_BLOCK_POS (CORANK_BLOCK * CORANK_STEPS) /* 2048 */
+#ifndef CORANK_TIE_HINTS
+#define CORANK_TIE_HINTS 1 /* prefix-tied pairs settled ahead of the walk,
+                              per thread (k_corank scout). Each one holds
+                              two aux records in flight (24 VGPRs on the
+                              48-B tier); 1 keeps cfg3's kernel at 5
+                              waves/SIMD, 2 and 3 drop it to 4 and 3 and
+                              lose more on tie-free windows than they gain
+                               */
+#endif
 #define CR_LOSER 0x80000000u
 #define CR_MASK 0x7FFFFFFFu
 
@@ -482,18 +583,12 @@ __global__ void k_corners(RunsDesc R, const uint64_t* pfx,
         uint64_t diag = (t - P.chunk_base) * CORANK_BLOCK_POS;
         uint64_t slo = diag > Nb ? diag - Nb : 0;
         uint64_t shi = diag < Na ? diag : Na;
-        while (slo < shi) {
-            uint64_t mid = (slo + shi) >> 1;
-            uint64_t pa = gpa[mid], pb = gpb[diag - mid - 1];
-            int c = (pa != pb)
-                        ? (pa < pb ? -1 : 1)
-                        : cmp_sfx_full<KB, TS>(R, aux, a, mid, b,
-                                               diag - mid - 1);
-            if (c < 0)
-                slo = mid + 1;
-            else
-                shi = mid;
-        }
+        slo = diag_split<uint64_t>(
+            slo, shi, diag, [&](uint64_t s) { return gpa[s]; },
+            [&](uint64_t s) { return gpb[s]; },
+            [&](uint64_t s, uint64_t u) {
+                return cmp_sfx_full<KB, TS>(R, aux, a, s, b, u) < 0;
+            });
         corners[t] = slo;
     }
 }
@@ -556,42 +651,121 @@ __global__ __launch_bounds__(BLK) void k_corank(
         if (d < L) {
             uint32_t slo = d > lenB ? d - lenB : 0;
             uint32_t shi = d < lenA ? d : lenA;
-            while (slo < shi) {
-                uint32_t mid = (slo + shi) >> 1;
-                uint64_t pa = sA[mid], pb = sB[d - mid - 1];
-                int c = (pa != pb) ? (pa < pb ? -1 : 1)
-                                   : cmp_sfx_full<KB, TS>(R, aux, a, iaS + mid,
-                                                          b, ibS + d - mid - 1);
-                if (c < 0)
-                    slo = mid + 1;
-                else
-                    shi = mid;
-            }
+            slo = diag_split<uint32_t>(
+                slo, shi, d, [&](uint32_t s) { return sA[s]; },
+                [&](uint32_t s) { return sB[s]; },
+                [&](uint32_t s, uint32_t u) {
+                    return cmp_sfx_full<KB, TS>(R, aux, a, iaS + s, b,
+                                                ibS + u) < 0;
+                });
             uint32_t ja = slo, jb = d - slo;
             uint32_t dend = d + STEPS;
             if (dend > L) dend = L;
 
+            /* Scout: a prefix-only two-pointer sweep over the staged
+             * entries this thread can reach notes the first M pairs with
+             * equal prefixes; their aux records are then fetched together
+             * and each pair is settled once, ahead of the walk, so the
+             * walk's serial steps do not each wait on a dependent global
+             * load. The notes are hints only: the walk looks a tied pair
+             * up here and settles it itself when it is not noted (more
+             * than M ties, prefix groups wider than 1x1, keys tied through
+             * the staged bytes), so ordering never depends on the sweep's
+             * provisional "consume both" rule. */
+            constexpr int M = CORANK_TIE_HINTS;
+            uint32_t hx[M], hy[M];
+            uint32_t hbits = 0; /* per hint m: bit 3m valid, 3m+1 keys
+                                   equal, 3m+2 a first */
+            #pragma unroll
+            for (int m = 0; m < M; m++) hx[m] = hy[m] = ~0u;
+            {
+                uint32_t nh = 0, x = ja, y = jb, c = d;
+                while (c < dend && x < lenA && y < lenB && nh < M) {
+                    uint64_t pa = sA[x], pb = sB[y];
+                    if (pa < pb) {
+                        x++, c++;
+                    } else if (pa > pb) {
+                        y++, c++;
+                    } else {
+                        #pragma unroll
+                        for (int m = 0; m < M; m++)
+                            if ((int)nh == m) hx[m] = x, hy[m] = y;
+                        nh++, x++, y++, c += 2;
+                    }
+                }
+                const AuxT<KB, TS>* xa = aux + R.entry_base[a] + iaS;
+                const AuxT<KB, TS>* xb = aux + R.entry_base[b] + ibS;
+                AuxT<KB, TS> ra[M], rb[M];
+                #pragma unroll
+                for (int m = 0; m < M; m++)
+                    if (m < (int)nh) {
+                        ra[m] = xa[hx[m]];
+                        rb[m] = xb[hy[m]];
+                    }
+                #pragma unroll
+                for (int m = 0; m < M; m++)
+                    if (m < (int)nh) {
+                        bool deep;
+                        int k = cmp_keys_rec<KB, TS>(ra[m], rb[m], deep);
+                        bool first = k < 0;
+                        if (k == 0 && !deep) {
+                            if constexpr (TS) {
+                                first = ra[m].ts_hi != rb[m].ts_hi
+                                            ? ra[m].ts_hi < rb[m].ts_hi
+                                        : ra[m].ts_lo != rb[m].ts_lo
+                                            ? ra[m].ts_lo < rb[m].ts_lo
+                                            : a < b;
+                            } else {
+                                first = cmp_ts_run_blob(R, a, iaS + hx[m], b,
+                                                        ibS + hy[m]) < 0;
+                            }
+                        }
+                        if (!deep)
+                            hbits |= (1u | (k == 0 ? 2u : 0u) |
+                                      (first ? 4u : 0u)) << (3 * m);
+                    }
+            }
+
             for (uint32_t pos = d; pos < dend; pos++) {
                 bool take_a;
+                bool both = false; /* this step compared (ja, jb) */
+                bool keq = false;  /* ... and their keys are equal    */
                 if (ja >= lenA)
                     take_a = false;
                 else if (jb >= lenB)
                     take_a = true;
                 else {
+                    both = true;
                     uint64_t pa = sA[ja], pb = sB[jb];
-                    take_a = (pa != pb)
-                                 ? (pa < pb)
-                                 : (cmp_sfx_full<KB, TS>(R, aux, a, iaS + ja, b,
-                                                         ibS + jb) < 0);
+                    if (pa != pb) {
+                        take_a = pa < pb;
+                    } else {
+                        uint32_t h = 0;
+                        #pragma unroll
+                        for (int m = 0; m < M; m++)
+                            if (hx[m] == ja && hy[m] == jb)
+                                h = hbits >> (3 * m);
+                        if (h & 1u) {
+                            keq = h & 2u;
+                            take_a = h & 4u;
+                        } else {
+                            take_a = tie_eval<KB, TS>(R, aux, a, iaS + ja, b,
+                                                      ibS + jb, keq);
+                        }
+                    }
                 }
+                /* The entry taken is superseded when the other run's next
+                 * entry carries the same key. With both cursors inside the
+                 * window that next entry is the one just compared, so the
+                 * answer is already known; only a cursor at the window's
+                 * end looks past the staged segment. */
                 if (take_a) {
                     uint64_t gib = ibS + jb;
                     uint32_t v = (uint32_t)gib;
-                    /* next b entry: staged, or first beyond the window */
-                    if (gib < Nb) {
-                        uint64_t pb =
-                            (jb < lenB) ? sB[jb] : gpb[gib];
-                        if (pb == sA[ja] &&
+                    if (both) {
+                        if (keq) v |= CR_LOSER;
+                    } else if (gib < Nb) {
+                        if (gpb[gib] == sA[ja] &&
                             cmp_keys_sfx<KB, TS>(R, aux, a, iaS + ja, b,
                                                  gib) == 0)
                             v |= CR_LOSER;
@@ -601,10 +775,10 @@ __global__ __launch_bounds__(BLK) void k_corank(
                 } else {
                     uint64_t gia = iaS + ja;
                     uint32_t v = (uint32_t)gia;
-                    if (gia < Na) {
-                        uint64_t pa =
-                            (ja < lenA) ? sA[ja] : gpa[gia];
-                        if (pa == sB[jb] &&
+                    if (both) {
+                        if (keq) v |= CR_LOSER;
+                    } else if (gia < Na) {
+                        if (gpa[gia] == sB[jb] &&
                             cmp_keys_sfx<KB, TS>(R, aux, b, ibS + jb, a,
                                                  gia) == 0)
                             v |= CR_LOSER;
@@ -729,17 +903,45 @@ struct RankRecPacked {
     }
 };
 
+/* The step's totals stay on the device: the emit thread that owns the
+ * last rank derives them from its scan value and stores them here, and
+ * k_winmap / k_copy read them from here, so no host round trip sits
+ * between emit and copy. On a flagged input (d_err set; prepare and
+ * rank-reduce are complete in stream order) the totals are zero, so a
+ * corrupt index can never drive the copy. The host reads the record once,
+ * after the copy. */
+struct StepTotals {
+    uint64_t total_out; /* output data bytes */
+    uint64_t n_surv;    /* surviving entries */
+    uint64_t err;       /* d_err[0] as the emit kernel saw it */
+};
+
+__device__ __forceinline__ void store_totals(StepTotals* tot,
+                                             const uint32_t* err,
+                                             const RankRec& last,
+                                             uint64_t last_off,
+                                             uint64_t last_pos) {
+    uint32_t e = *err;
+    uint64_t kept = (last.src & RR_KEEP) ? 1 : 0;
+    tot->total_out = e ? 0 : last_off + (kept ? last.full_size : 0);
+    tot->n_surv = e ? 0 : last_pos + kept;
+    tot->err = e;
+}
+
 /* Output index records are the input format: offset u64 | key_size u32 |
  * full_size u32 (entry_writer.rs:79-87, offsets recomputed from 0).
  * src_map gets the ABSOLUTE device address of each survivor's bytes. */
 __global__ void k_emit(RunsDesc R, const RankRec* rrec,
                        const uint64_t* dst_off, const uint32_t* pos,
                        uint64_t total, uint8_t* out_index,
-                       uint64_t* src_map) {
+                       uint64_t* src_map, const uint32_t* err,
+                       StepTotals* tot) {
     uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
          g < total; g += stride) {
         RankRec m = rrec[g];
+        if (g + 1 == total)
+            store_totals(tot, err, m, dst_off[g], pos[g]);
         if (!(m.src & RR_KEEP)) continue;
         uint64_t p = pos[g];
         uint8_t* rec = out_index + p * 16;
@@ -756,11 +958,15 @@ __global__ void k_emit(RunsDesc R, const RankRec* rrec,
  * from one u64 (low 38 bits = byte offset, high 26 = survivor index). */
 __global__ void k_emit_packed(RunsDesc R, const RankRec* rrec,
                               const uint64_t* packed, uint64_t total,
-                              uint8_t* out_index, uint64_t* src_map) {
+                              uint8_t* out_index, uint64_t* src_map,
+                              const uint32_t* err, StepTotals* tot) {
     uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
          g < total; g += stride) {
         RankRec m = rrec[g];
+        if (g + 1 == total)
+            store_totals(tot, err, m, packed[g] & PK_MASK,
+                         packed[g] >> PK_SHIFT);
         if (!(m.src & RR_KEEP)) continue;
         uint64_t v = packed[g];
         uint64_t p = v >> PK_SHIFT;
@@ -791,9 +997,9 @@ __global__ void k_emit_packed(RunsDesc R, const RankRec* rrec,
 
 /* Per destination window, the largest survivor p with offset(p) <= window
  * start — one thread per window (parallel), consumed by k_copy. */
-__global__ void k_winmap(const uint8_t* out_index, uint64_t n_surv,
-                         uint64_t total_bytes, uint32_t win,
-                         uint32_t* win_p0) {
+__global__ void k_winmap(const uint8_t* out_index, const StepTotals* tot,
+                         uint32_t win, uint32_t* win_p0) {
+    const uint64_t n_surv = tot->n_surv, total_bytes = tot->total_out;
     uint64_t n_windows = (total_bytes + win - 1) / win;
     uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -814,8 +1020,10 @@ __global__ void k_winmap(const uint8_t* out_index, uint64_t n_surv,
 template <int BLK, int WIN>
 __global__ __launch_bounds__(BLK) void k_copy(
     const uint8_t* out_index, const uint64_t* src_map,
-    const uint32_t* win_p0, uint64_t n_surv, uint64_t total_bytes,
-    uint8_t* out_data) {
+    const uint32_t* win_p0, const StepTotals* tot, uint8_t* out_data) {
+    /* the grid is sized from an upper bound on the output; blocks whose
+     * first window lies past the real end fall straight through */
+    const uint64_t n_surv = tot->n_surv, total_bytes = tot->total_out;
     constexpr int SPAN = WIN / 32 + 4;
     constexpr int GRAN = WIN / 16;
     __shared__ uint64_t s_off[SPAN + 1];
@@ -1251,6 +1459,8 @@ struct dbeel_gpu_job {
     uint64_t total_chunks = 0;
     uint32_t* d_winp0 = nullptr; /* copy window -> first survivor       */
     uint64_t* d_corners = nullptr; /* corank chunk start corners        */
+    StepTotals* d_tot = nullptr; /* step totals, written by emit         */
+    StepTotals* h_tot = nullptr; /* pinned: the one read per step        */
     uint64_t total_entries = 0;
     uint64_t total_data_bytes = 0;
     uint64_t input_bytes = 0;
@@ -1395,6 +1605,8 @@ static int job_create_impl(const dbeel_run_view* runs, size_t n_runs,
     JOB_CHECK(hipMalloc(&job->d_outdata, total_data ? total_data : 16));
     JOB_CHECK(hipMalloc(&job->d_err, 2 * sizeof(uint32_t)));
     JOB_CHECK(hipMalloc(&job->d_pfx, n * sizeof(uint64_t)));
+    JOB_CHECK(hipMalloc(&job->d_tot, sizeof(StepTotals)));
+    JOB_CHECK(hipHostMalloc(&job->h_tot, sizeof(StepTotals)));
     uint32_t max_job_runs = 1;
     {
         for (size_t j = 0; j < n_jobs; j++)
@@ -1675,6 +1887,8 @@ extern "C" void dbeel_gpu_job_destroy(dbeel_gpu_job* job) {
     hipFree(job->d_pairs);
     hipFree(job->d_winp0);
     hipFree(job->d_corners);
+    hipFree(job->d_tot);
+    if (job->h_tot) hipHostFree(job->h_tot);
     for (int i = 0; i < 8; i++)
         if (job->ev[i]) hipEventDestroy(job->ev[i]);
     if (job->stream) hipStreamDestroy(job->stream);
@@ -1942,11 +2156,23 @@ static uint32_t pick_grid(uint64_t work_items, uint32_t block) {
  * 512 threads (fewer window transitions+barriers per block); 4 KiB
  * survivors (cfg5) want MORE blocks (grid 16384) at the default window
  * (the 4096 cap left most waves parked); sub-512-B survivors keep the
- * default. Env DBEEL_COPY_VARIANT / DBEEL_COPY_GRID override for A/Bs. */
+ * default. Env DBEEL_COPY_VARIANT / DBEEL_COPY_GRID override for A/Bs.
+ *
+ * The real totals live on the device (StepTotals), so the host decides
+ * from what it knows before the step: the grid from an upper bound on the
+ * output (the input's data bytes; surplus blocks and windows exit), the
+ * variant from the INPUT's average entry size. The three classes are wide
+ * (< 512, 512..2048, > 2048 B) and the BASELINE shapes sit well inside
+ * them on both measures (cfg2/cfg4 304 B in, 304 B out; cfg3 1037 B in,
+ * 1088 B out; cfg5 ~4.07 KiB in, ~4.15 KiB out), so this picks what the
+ * output average picked. The two can differ only when dropped tombstones
+ * or superseded entries shift the average across a class boundary (say
+ * 60% dropped tombstones among 1 KiB values: 470 B in, 1088 B out); every
+ * variant is correct for every size, the choice is a speed matter only. */
 static void launch_copy(hipStream_t s, const uint8_t* out_index,
                         const uint64_t* src_map, uint32_t* win_p0,
-                        uint64_t n_surv, uint64_t total_out,
-                        uint8_t* out_data) {
+                        const StepTotals* tot, uint64_t in_entries,
+                        uint64_t in_bytes, uint8_t* out_data) {
     int variant = -1;
     if (const char* v = getenv("DBEEL_COPY_VARIANT")) variant = atoi(v);
     uint64_t gcap = 0;
@@ -1955,7 +2181,7 @@ static void launch_copy(hipStream_t s, const uint8_t* out_index,
         if (v >= 64) gcap = (uint64_t)v;
     }
     if (variant < 0) {
-        uint64_t avg = n_surv ? total_out / n_surv : 0;
+        uint64_t avg = in_entries ? in_bytes / in_entries : 0;
         if (avg > 2048) {
             variant = 0; /* 4 KiB-class: more blocks, small windows */
             if (!gcap) gcap = 16384;
@@ -1973,18 +2199,19 @@ static void launch_copy(hipStream_t s, const uint8_t* out_index,
                    : (variant == 4) ? 65536
                                     : 16384;
     uint32_t blk = (variant >= 2) ? 512 : 256;
-    uint64_t windows = (total_out + win - 1) / win;
+    uint64_t windows = (in_bytes + win - 1) / win; /* upper bound */
+    if (!windows) return;
     uint32_t grid = windows > gcap ? (uint32_t)gcap : (uint32_t)windows;
     hipLaunchKernelGGL(k_winmap, dim3(pick_grid(windows, 256)), dim3(256),
-                       0, s, out_index, n_surv, total_out, win, win_p0);
-    void (*kc)(const uint8_t*, const uint64_t*, const uint32_t*, uint64_t,
-               uint64_t, uint8_t*) = k_copy<256, 16384>;
+                       0, s, out_index, tot, win, win_p0);
+    void (*kc)(const uint8_t*, const uint64_t*, const uint32_t*,
+               const StepTotals*, uint8_t*) = k_copy<256, 16384>;
     if (variant == 1) kc = k_copy<256, 8192>;
     if (variant == 2) kc = k_copy<512, 16384>;
     if (variant == 3) kc = k_copy<512, 32768>;
     if (variant == 4) kc = k_copy<512, 65536>;
     hipLaunchKernelGGL(kc, dim3(grid), dim3(blk), 0, s, out_index, src_map,
-                       win_p0, n_surv, total_out, out_data);
+                       win_p0, tot, out_data);
 }
 
 extern "C" int dbeel_gpu_job_run(dbeel_gpu_job* job, int keep_tombstones,
@@ -2094,31 +2321,30 @@ extern "C" int dbeel_gpu_job_run(dbeel_gpu_job* job, int keep_tombstones,
         if (packed)
             hipLaunchKernelGGL(k_emit_packed, dim3(grid), dim3(256), 0, s,
                                job->desc, job->d_rank, job->d_dstoff, n,
-                               job->d_outindex, job->d_srcmap);
+                               job->d_outindex, job->d_srcmap, job->d_err,
+                               job->d_tot);
         else
             hipLaunchKernelGGL(k_emit, dim3(grid), dim3(256), 0, s,
                                job->desc, job->d_rank, job->d_dstoff,
                                job->d_pos, n, job->d_outindex,
-                               job->d_srcmap);
+                               job->d_srcmap, job->d_err, job->d_tot);
+    } else {
+        HIP_CHECK(hipMemsetAsync(job->d_tot, 0, sizeof(StepTotals), s));
     }
     HIP_CHECK(hipEventRecord(job->ev[3], s));
 
-    /* Need totals on host to size/launch the copy; one small sync. */
-    RankRec last_rec = {};
-    uint64_t last_off = 0;
-    uint32_t last_pos = 0;
-    uint32_t err = 0;
-    if (n) {
-        HIP_CHECK(hipMemcpyAsync(&last_rec, job->d_rank + (n - 1), 16,
-                                 hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipMemcpyAsync(&last_off, job->d_dstoff + (n - 1), 8,
-                                 hipMemcpyDeviceToHost, s));
-        if (!packed)
-            HIP_CHECK(hipMemcpyAsync(&last_pos, job->d_pos + (n - 1), 4,
-                                     hipMemcpyDeviceToHost, s));
-    }
-    HIP_CHECK(hipMemcpyAsync(&err, job->d_err, 4, hipMemcpyDeviceToHost, s));
+    /* The copy takes its totals from the device record: nothing to wait
+     * for here. One sync and one 24-B read end the step. */
+    HIP_CHECK(hipEventRecord(job->ev[4], s));
+    if (n)
+        launch_copy(s, job->d_outindex, job->d_srcmap, job->d_winp0,
+                    job->d_tot, n, job->total_data_bytes, job->d_outdata);
+    HIP_CHECK(hipEventRecord(job->ev[5], s));
+    HIP_CHECK(hipMemcpyAsync(job->h_tot, job->d_tot, sizeof(StepTotals),
+                             hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipGetLastError());
+    uint32_t err = (uint32_t)job->h_tot->err;
     if (err) {
         set_err(err & DERR_UNSORTED
                     ? "input run not strictly sorted by unique keys "
@@ -2126,22 +2352,9 @@ extern "C" int dbeel_gpu_job_run(dbeel_gpu_job* job, int keep_tombstones,
                     : "corrupt entry/index record");
         return DBEEL_ERR_CORRUPT;
     }
-    if (packed) {
-        last_pos = (uint32_t)(last_off >> PK_SHIFT);
-        last_off &= PK_MASK;
-    }
     job->last_scan_packed = packed ? 1 : 0;
-    uint64_t last_kept = (n && (last_rec.src & RR_KEEP)) ? 1 : 0;
-    uint64_t total_out = last_off + (last_kept ? last_rec.full_size : 0);
-    uint64_t n_surv = (uint64_t)last_pos + last_kept;
-
-    HIP_CHECK(hipEventRecord(job->ev[4], s));
-    if (total_out)
-        launch_copy(s, job->d_outindex, job->d_srcmap, job->d_winp0,
-                    n_surv, total_out, job->d_outdata);
-    HIP_CHECK(hipEventRecord(job->ev[5], s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    HIP_CHECK(hipGetLastError());
+    uint64_t total_out = job->h_tot->total_out;
+    uint64_t n_surv = job->h_tot->n_surv;
 
     job->out_data_len = total_out;
     job->out_entries = n_surv;
@@ -3622,23 +3835,16 @@ extern "C" int dbeel_gpu_scan(const dbeel_run_view* runs, size_t n_runs,
             job->d_pos, (uint32_t)0, n, rocprim::plus<uint32_t>(), s);
         hipLaunchKernelGGL(k_emit, dim3(pick_grid(n, 256)), dim3(256), 0,
                            s, job->desc, job->d_rank, job->d_dstoff,
-                           job->d_pos, n, job->d_outindex, job->d_srcmap);
-    }
-    RankRec last_rec = {};
-    uint64_t last_off = 0;
-    uint32_t last_pos = 0, derr = 0;
-    if (e == hipSuccess && n) {
-        e = hipMemcpyAsync(&last_rec, job->d_rank + (n - 1), 16,
-                           hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(&last_off, job->d_dstoff + (n - 1), 8,
-                               hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(&last_pos, job->d_pos + (n - 1), 4,
-                               hipMemcpyDeviceToHost, s);
+                           job->d_pos, n, job->d_outindex, job->d_srcmap,
+                           job->d_err, job->d_tot);
+        launch_copy(s, job->d_outindex, job->d_srcmap, job->d_winp0,
+                    job->d_tot, n, job->total_data_bytes, job->d_outdata);
+    } else if (e == hipSuccess) {
+        e = hipMemsetAsync(job->d_tot, 0, sizeof(StepTotals), s);
     }
     if (e == hipSuccess)
-        e = hipMemcpyAsync(&derr, job->d_err, 4, hipMemcpyDeviceToHost, s);
+        e = hipMemcpyAsync(job->h_tot, job->d_tot, sizeof(StepTotals),
+                           hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e == hipSuccess) e = hipGetLastError();
 
@@ -3647,28 +3853,14 @@ extern "C" int dbeel_gpu_scan(const dbeel_run_view* runs, size_t n_runs,
     if (e != hipSuccess) {
         set_err("scan failed: %s", hipGetErrorString(e));
         ret = DBEEL_ERR_HIP;
-    } else if (derr) {
+    } else if (job->h_tot->err) {
         set_err("corrupt entry/index record");
         ret = DBEEL_ERR_CORRUPT;
     } else {
-        uint64_t last_kept = (n && (last_rec.src & RR_KEEP)) ? 1 : 0;
-        uint64_t total_out =
-            last_off + (last_kept ? last_rec.full_size : 0);
-        uint64_t n_surv = (uint64_t)last_pos + last_kept;
-        if (total_out)
-            launch_copy(s, job->d_outindex, job->d_srcmap, job->d_winp0,
-                        n_surv, total_out, job->d_outdata);
-        e = hipStreamSynchronize(s);
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e != hipSuccess) {
-            set_err("scan copy failed: %s", hipGetErrorString(e));
-            ret = DBEEL_ERR_HIP;
-        } else {
-            job->out_data_len = total_out;
-            job->out_entries = n_surv;
-            job->have_result = true;
-            ret = dbeel_gpu_job_fetch(job, out);
-        }
+        job->out_data_len = job->h_tot->total_out;
+        job->out_entries = job->h_tot->n_surv;
+        job->have_result = true;
+        ret = dbeel_gpu_job_fetch(job, out);
     }
     hipFree(d_kb);
     hipFree(d_ranges);
