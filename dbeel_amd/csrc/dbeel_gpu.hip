@@ -49,8 +49,10 @@
  *                  + prefix array, batched search with the on-device
  *                  bloom prefilter, value gather; k_reader_adopt turns
  *                  a compaction output into a resident table (prefixes
- *                  + filter bits in one pass) for the live table list.
- *   host side    : resident jobs, batched independent jobs (one launch
+ *                  + filter bits in one pass) for the live table list;
+ *                  k_reader_scan_bounds/_flag/_emit page the migration
+ *                  scan over the resident tables into caller buffers.
+ *   host side   : resident jobs, batched independent jobs (one launch
  *                  set, per-job output slicing), streamed pinned ingest
  *                  with copy/compute overlap, sliced compaction for
  *                  inputs larger than HBM, device bloom build.
@@ -2875,6 +2877,18 @@ struct ReaderTable {
     const uint8_t* index() const { return d_run + 16 + data_len; }
 };
 
+/* What a paged-scan page leaves on the device for the host's one read:
+ * the copy's totals (st, read on-device by k_winmap / k_copy) plus where
+ * the cursor goes. */
+struct ScanPageTotals {
+    StepTotals st;      /* bytes / entries TAKEN by the page; err unused   */
+    uint64_t next;      /* window position of the first survivor not taken,
+                           or the window length when all were taken        */
+    uint64_t next_full; /* that survivor's full_size, 0 when there is none  */
+};
+
+struct dbeel_gpu_reader_scan;
+
 struct dbeel_gpu_reader {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -2900,7 +2914,23 @@ struct dbeel_gpu_reader {
     uint8_t* d_values = nullptr;
     uint64_t values_cap = 0;
     unsigned long long* d_stats = nullptr;
+    /* paged scans: generation is bumped by every edit of the table list
+     * (a scan from an older generation is stale); the per-page scratch, the
+     * device page buffer and the copy's window map grow on demand and are
+     * reused by every scan of this reader */
+    uint64_t generation = 0;
+    std::vector<dbeel_gpu_reader_scan*> scans;
+    uint8_t* d_scan = nullptr;
+    uint64_t scan_cap = 0;
+    uint8_t* d_page = nullptr;
+    uint64_t page_cap = 0;
+    uint32_t* d_scanwin = nullptr;
+    uint64_t scanwin_cap = 0;
+    ScanPageTotals* d_scantot = nullptr;
+    ScanPageTotals* h_scantot = nullptr; /* pinned */
 };
+
+static void reader_end_scans(dbeel_gpu_reader* rd);
 
 static hipError_t reader_reserve(void** p, uint64_t* cap, uint64_t need) {
     if (need <= *cap) return hipSuccess;
@@ -3003,6 +3033,7 @@ extern "C" void dbeel_gpu_reader_close(dbeel_gpu_reader* rd) {
     if (rd->device >= 0) (void)hipSetDevice(rd->device);
     if (rd->stream) (void)hipStreamSynchronize(rd->stream);
     dbeel_gpu_reader_compact_abort(rd);
+    reader_end_scans(rd);
     for (ReaderTable& t : rd->tables) table_free(t);
     (void)hipFree(rd->d_blooms);
     (void)hipFree(rd->d_keys);
@@ -3010,6 +3041,11 @@ extern "C" void dbeel_gpu_reader_close(dbeel_gpu_reader* rd) {
     (void)hipFree(rd->d_scantmp);
     (void)hipFree(rd->d_values);
     (void)hipFree(rd->d_stats);
+    (void)hipFree(rd->d_scan);
+    (void)hipFree(rd->d_page);
+    (void)hipFree(rd->d_scanwin);
+    (void)hipFree(rd->d_scantot);
+    if (rd->h_scantot) (void)hipHostFree(rd->h_scantot);
     for (int i = 0; i < 7; i++)
         if (rd->ev[i]) (void)hipEventDestroy(rd->ev[i]);
     if (rd->stream) (void)hipStreamDestroy(rd->stream);
@@ -3246,6 +3282,7 @@ extern "C" int dbeel_gpu_reader_insert_run(dbeel_gpu_reader* rd, size_t pos,
         return DBEEL_ERR_CORRUPT;
     }
     rd->tables.insert(rd->tables.begin() + pos, t);
+    rd->generation++; /* open scans are stale from here on */
     /* a pending compaction keeps naming the same tables */
     for (uint32_t& p : rd->pending_pos)
         if (p >= pos) p++;
@@ -3487,6 +3524,7 @@ extern "C" int dbeel_gpu_reader_compact_commit(dbeel_gpu_reader* rd,
     }
     keep.insert(keep.begin() + out_pos, rd->pending);
     rd->tables.swap(keep);
+    rd->generation++; /* open scans are stale from here on */
     rd->pending = ReaderTable();
     rd->pending_pos.clear();
     rd->has_pending = false;
@@ -3866,6 +3904,516 @@ extern "C" int dbeel_gpu_scan(const dbeel_run_view* runs, size_t n_runs,
     hipFree(d_ranges);
     dbeel_gpu_job_destroy(job);
     return ret;
+}
+
+/* ------------------------------------------------------------------ */
+/* Paged scan over the resident tables (dbeel_gpu_reader_scan_*)      */
+/*                                                                    */
+/* dbeel_gpu_scan above loads every entry of every run, whatever the  */
+/* key range. Here the key range is resolved ONCE, per table, on the  */
+/* resident prefix arrays (k_reader_scan_bounds): the candidates are  */
+/* the concatenation over tables of [lower_bound(start),              */
+/* lower_bound(end)), and a page is a window of that space:           */
+/*   k_reader_scan_flag : candidate -> (table, entry); hash filter +  */
+/*                        first matching range; one RankRec + range   */
+/*                        id per candidate. No key compares.          */
+/*   rocPRIM scans      : survivor byte offsets and positions inside  */
+/*                        the window (the job pipeline's functors).   */
+/*   k_reader_scan_emit : capped emit — the survivors that fit the    */
+/*                        caller's data / index capacity form a       */
+/*                        prefix; index records, source addresses and */
+/*                        compacted range ids for those, plus the     */
+/*                        page totals and the next cursor position.   */
+/*   k_winmap / k_copy  : unchanged, into the reader's page buffer.   */
+/* ------------------------------------------------------------------ */
+
+/* Candidate space -> table entries, by value next to RunsDesc: table r
+ * owns the candidates [cend[r-1], cend[r]) and candidate c of it is entry
+ * c + adj[r] (adj = first in-range entry minus the table's candidate base,
+ * modulo 2^64). */
+struct ScanWin {
+    uint64_t cend[MAX_RUNS];
+    uint64_t adj[MAX_RUNS];
+};
+static_assert(sizeof(RunsDesc) + sizeof(ScanWin) + 128 <= 4096,
+              "k_reader_scan_flag arguments must fit the kernarg segment");
+
+#define SCAN_NO_RANGE 0xFFFFFFFFu
+#define SCAN_DEFAULT_CANDIDATES (1ull << 20)
+#define SCAN_MAX_CANDIDATES (1ull << 31) /* survivor positions are u32 */
+
+/* One thread per (table, bound): bounds[2r] = lower_bound(start_key),
+ * bounds[2r+1] = lower_bound(end_key) in table r; an absent bound gives 0 /
+ * count. k_reader_search's shape: bisect the prefixes, then settle the
+ * equal-prefix stretch (zero padding, bytes past 8, length) by a second
+ * bisection with full key compares on the blob — never a walk. */
+__global__ void k_reader_scan_bounds(RunsDesc R, ReaderPfx pfx,
+                                     const uint8_t* kbounds,
+                                     uint64_t start_len, uint64_t end_len,
+                                     int have_start, int have_end,
+                                     uint64_t* bounds) {
+    uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 2u * (uint32_t)R.n_runs) return;
+    const int r = (int)(t >> 1);
+    const bool is_end = t & 1;
+    const uint64_t n = R.count[r];
+    if (!(is_end ? have_end : have_start)) {
+        bounds[t] = is_end ? n : 0;
+        return;
+    }
+    const uint8_t* key = is_end ? kbounds + start_len : kbounds;
+    const uint64_t klen = is_end ? end_len : start_len;
+    const uint64_t qp = key_prefix(key, klen);
+    const uint64_t* P = pfx.p[r];
+    uint64_t lo = 0, hi = n; /* first prefix >= qp */
+    while (lo < hi) {
+        uint64_t mid = (lo + hi) >> 1;
+        if (P[mid] < qp)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    uint64_t a = lo, end = n; /* first prefix > qp */
+    while (a < end) {
+        uint64_t mid = (a + end) >> 1;
+        if (P[mid] <= qp)
+            a = mid + 1;
+        else
+            end = mid;
+    }
+    /* [lo, end) share the bound's prefix and are in key order: the first
+     * one >= the bound is the answer (end when there is none) */
+    while (lo < end) {
+        uint64_t mid = (lo + end) >> 1;
+        EView m;
+        if (!load_entry(R, r, mid, m)) { /* validated at open */
+            end = mid;
+            continue;
+        }
+        if (cmp_keys(m.key, m.klen, key, klen) < 0)
+            lo = mid + 1;
+        else
+            end = mid;
+    }
+    bounds[t] = lo;
+}
+
+__global__ void k_reader_scan_flag(RunsDesc R, ScanWin W, uint64_t c0,
+                                   uint64_t m, const uint32_t* rstart,
+                                   const uint32_t* rend, uint32_t n_ranges,
+                                   RankRec* rrec, uint32_t* rid) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < m;
+         w += stride) {
+        const uint64_t c = c0 + w;
+        int r = 0;
+        while (r + 1 < R.n_runs && c >= W.cend[r]) r++;
+        const uint64_t i = c + W.adj[r];
+        EView e;
+        if (i >= R.count[r] || !load_entry(R, r, i, e)) {
+            /* cannot happen on tables validated at open; stay memory safe */
+            RankRec z = {0, 8, 32};
+            rrec[w] = z;
+            rid[w] = SCAN_NO_RANGE;
+            continue;
+        }
+        uint32_t id = SCAN_NO_RANGE;
+        if (n_ranges) {
+            const uint32_t h = murmur3_32(e.key, e.klen, 0);
+            for (uint32_t j = 0; j < n_ranges; j++)
+                if (hash_between(h, rstart[j], rend[j])) {
+                    id = j;
+                    break;
+                }
+        }
+        const bool keep = n_ranges == 0 || id != SCAN_NO_RANGE;
+        RankRec rec;
+        rec.src = ((uint64_t)r << 48) | e.off | (keep ? RR_KEEP : 0);
+        rec.key_size = e.key_size;
+        rec.full_size = e.full_size;
+        rrec[w] = rec;
+        rid[w] = id;
+    }
+}
+
+/* Does everything up to AND INCLUDING window position g fit the page?
+ * off / pos are the exclusive survivor sums at g. Both sums only grow with
+ * g, so the positions that fit form a prefix of the window. */
+__device__ __forceinline__ bool scan_page_fits(const RankRec& m, uint64_t off,
+                                               uint32_t pos,
+                                               uint64_t data_cap,
+                                               uint64_t max_entries) {
+    const bool kept = m.src & RR_KEEP;
+    return off + (kept ? m.full_size : 0u) <= data_cap &&
+           (uint64_t)pos + (kept ? 1u : 0u) <= max_entries;
+}
+
+/* Capped emit. Exactly one thread owns the page totals: the last position
+ * that fits (its successor, if any, is then a survivor that does not), or
+ * position 0 when not even that fits. Plain vector stores, no atomics. */
+__global__ void k_reader_scan_emit(RunsDesc R, const RankRec* rrec,
+                                   const uint32_t* rid,
+                                   const uint64_t* dst_off,
+                                   const uint32_t* pos, uint64_t m,
+                                   uint64_t data_cap, uint64_t max_entries,
+                                   uint8_t* out_index, uint64_t* src_map,
+                                   uint32_t* rid_out, ScanPageTotals* tot) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < m;
+         g += stride) {
+        const RankRec rec = rrec[g];
+        const uint64_t off = dst_off[g];
+        const uint32_t p = pos[g];
+        if (!scan_page_fits(rec, off, p, data_cap, max_entries)) {
+            if (g == 0) {
+                tot->st.total_out = 0;
+                tot->st.n_surv = 0;
+                tot->st.err = 0;
+                tot->next = 0;
+                tot->next_full = rec.full_size;
+            }
+            continue;
+        }
+        const bool kept = rec.src & RR_KEEP;
+        bool last = g + 1 == m;
+        uint64_t next_full = 0;
+        if (!last) {
+            const RankRec nx = rrec[g + 1];
+            last = !scan_page_fits(nx, dst_off[g + 1], pos[g + 1], data_cap,
+                                   max_entries);
+            next_full = nx.full_size;
+        }
+        if (last) {
+            tot->st.total_out = off + (kept ? rec.full_size : 0u);
+            tot->st.n_surv = (uint64_t)p + (kept ? 1u : 0u);
+            tot->st.err = 0;
+            tot->next = g + 1;
+            tot->next_full = next_full;
+        }
+        if (!kept) continue;
+        uint8_t* out = out_index + (uint64_t)p * 16;
+        __builtin_memcpy(out, &off, 8);
+        __builtin_memcpy(out + 8, &rec.key_size, 4);
+        __builtin_memcpy(out + 12, &rec.full_size, 4);
+        src_map[p] = (uint64_t)(R.data[(rec.src >> 48) & 0x7FFF] +
+                                (rec.src & RR_OFF_MASK));
+        rid_out[p] = rid[g];
+    }
+}
+
+struct dbeel_gpu_reader_scan {
+    dbeel_gpu_reader* rd = nullptr;
+    uint64_t generation = 0; /* rd->generation at begin */
+    ScanWin win{};
+    uint64_t total = 0;  /* candidates in all tables */
+    uint64_t cursor = 0; /* next candidate to examine */
+    uint64_t max_candidates = 0;
+    uint32_t* d_ranges = nullptr; /* starts | ends */
+    uint32_t n_ranges = 0;
+};
+
+static void scan_free(dbeel_gpu_reader_scan* sc) {
+    (void)hipFree(sc->d_ranges);
+    delete sc;
+}
+
+static void reader_end_scans(dbeel_gpu_reader* rd) {
+    for (dbeel_gpu_reader_scan* sc : rd->scans) scan_free(sc);
+    rd->scans.clear();
+}
+
+extern "C" void dbeel_gpu_reader_scan_end(dbeel_gpu_reader_scan* sc) {
+    if (!sc) return;
+    dbeel_gpu_reader* rd = sc->rd;
+    if (rd->device >= 0) (void)hipSetDevice(rd->device);
+    for (size_t i = 0; i < rd->scans.size(); i++)
+        if (rd->scans[i] == sc) {
+            rd->scans.erase(rd->scans.begin() + i);
+            break;
+        }
+    scan_free(sc);
+}
+
+extern "C" int dbeel_gpu_reader_scan_begin(
+    dbeel_gpu_reader* rd, const uint8_t* start_key, size_t start_key_len,
+    const uint8_t* end_key, size_t end_key_len, const uint32_t* range_starts,
+    const uint32_t* range_ends, size_t n_ranges, uint64_t max_candidates,
+    dbeel_gpu_reader_scan** out) {
+    g_err[0] = 0;
+    if (out) *out = nullptr;
+    if (!rd || !out) {
+        set_err("reader_scan_begin: null reader or out");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if ((start_key_len && !start_key) || (end_key_len && !end_key)) {
+        set_err("reader_scan_begin: key length given without its pointer");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (n_ranges && (!range_starts || !range_ends)) {
+        set_err("reader_scan_begin: n_ranges given without the range arrays");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (n_ranges >= SCAN_NO_RANGE) {
+        set_err("reader_scan_begin: too many hash ranges");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    HIP_CHECK(hipSetDevice(rd->device));
+    hipStream_t s = rd->stream;
+    if (!rd->d_scantot)
+        HIP_CHECK(hipMalloc(&rd->d_scantot, sizeof(ScanPageTotals)));
+    if (!rd->h_scantot)
+        HIP_CHECK(hipHostMalloc(&rd->h_scantot, sizeof(ScanPageTotals)));
+    dbeel_gpu_reader_scan* sc = new (std::nothrow) dbeel_gpu_reader_scan();
+    if (!sc) {
+        set_err("host alloc failed");
+        return DBEEL_ERR_OOM;
+    }
+    sc->rd = rd;
+    sc->generation = rd->generation;
+    sc->n_ranges = (uint32_t)n_ranges;
+    sc->max_candidates = max_candidates ? max_candidates
+                                        : SCAN_DEFAULT_CANDIDATES;
+    if (sc->max_candidates > SCAN_MAX_CANDIDATES)
+        sc->max_candidates = SCAN_MAX_CANDIDATES;
+
+    const int n_runs = rd->desc.n_runs;
+    const uint64_t kb_len = (uint64_t)start_key_len + end_key_len;
+    uint64_t hb[2 * MAX_RUNS];
+    uint8_t* d_kb = nullptr; /* bound keys | 2 * n_runs bounds, 8-B aligned */
+    const uint64_t kb_pad = (kb_len + 7) & ~7ull;
+    hipError_t e = hipSuccess;
+    if (n_ranges) {
+        e = hipMalloc(&sc->d_ranges, 2 * n_ranges * sizeof(uint32_t));
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(sc->d_ranges, range_starts, n_ranges * 4,
+                               hipMemcpyHostToDevice, s);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(sc->d_ranges + n_ranges, range_ends,
+                               n_ranges * 4, hipMemcpyHostToDevice, s);
+    }
+    if (e == hipSuccess && n_runs) {
+        e = hipMalloc(&d_kb, kb_pad + sizeof hb);
+        if (e == hipSuccess && start_key_len)
+            e = hipMemcpyAsync(d_kb, start_key, start_key_len,
+                               hipMemcpyHostToDevice, s);
+        if (e == hipSuccess && end_key_len)
+            e = hipMemcpyAsync(d_kb + start_key_len, end_key, end_key_len,
+                               hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) {
+            uint64_t* d_bounds = (uint64_t*)(d_kb + kb_pad);
+            hipLaunchKernelGGL(k_reader_scan_bounds, dim3(1),
+                               dim3(2 * MAX_RUNS), 0, s, rd->desc, rd->pfx,
+                               d_kb, (uint64_t)start_key_len,
+                               (uint64_t)end_key_len, start_key ? 1 : 0,
+                               end_key ? 1 : 0, d_bounds);
+            e = hipMemcpyAsync(hb, d_bounds,
+                               2 * (size_t)n_runs * sizeof(uint64_t),
+                               hipMemcpyDeviceToHost, s);
+        }
+    }
+    /* the caller's keys and ranges are read by the async copies above */
+    hipError_t se = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = se;
+    if (e == hipSuccess) e = hipGetLastError();
+    (void)hipFree(d_kb);
+    if (e != hipSuccess) {
+        set_err("reader_scan_begin: %s", hipGetErrorString(e));
+        scan_free(sc);
+        return e == hipErrorOutOfMemory ? DBEEL_ERR_OOM : DBEEL_ERR_HIP;
+    }
+    uint64_t base = 0;
+    for (int r = 0; r < n_runs; r++) {
+        uint64_t lo = hb[2 * r], hi = hb[2 * r + 1];
+        const uint64_t n = rd->desc.count[r];
+        if (lo > n) lo = n;
+        if (hi > n) hi = n;
+        if (hi < lo) hi = lo; /* start > end: nothing */
+        sc->win.adj[r] = lo - base;
+        base += hi - lo;
+        sc->win.cend[r] = base;
+    }
+    sc->total = base;
+    rd->scans.push_back(sc);
+    *out = sc;
+    return DBEEL_OK;
+}
+
+static inline uint64_t scan_align16(uint64_t v) { return (v + 15) & ~15ull; }
+
+extern "C" int dbeel_gpu_reader_scan_next(dbeel_gpu_reader_scan* sc,
+                                          uint8_t* data, size_t data_cap,
+                                          uint8_t* index, size_t index_cap,
+                                          uint32_t* range_ids,
+                                          dbeel_scan_page* page) {
+    g_err[0] = 0;
+    if (page) memset(page, 0, sizeof *page);
+    if (!sc || !page) {
+        set_err("reader_scan_next: null scan or page");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (!data || !index || data_cap == 0 || index_cap < 16) {
+        set_err("reader_scan_next: data and index buffers must be non-null, "
+                "data_cap > 0 and index_cap >= 16");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    dbeel_gpu_reader* rd = sc->rd;
+    if (sc->generation != rd->generation) {
+        set_err("reader_scan_next: stale scan (the table list changed since "
+                "scan_begin; start a new scan)");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    uint64_t m = sc->total - sc->cursor;
+    if (m > sc->max_candidates) m = sc->max_candidates;
+    if (m == 0) {
+        page->done = 1;
+        return DBEEL_OK;
+    }
+    const RunsDesc& D = rd->desc;
+    uint64_t resident = 0; /* no page can hold more than the tables do */
+    for (int r = 0; r < D.n_runs; r++) resident += D.data_len[r];
+    const uint64_t cap = data_cap < resident ? (uint64_t)data_cap : resident;
+    uint64_t max_entries = index_cap / 16;
+    if (max_entries > m) max_entries = m;
+
+    /* scratch: rrec | dst_off | pos | rid | out_index | src_map | rid_out */
+    const uint64_t o_rrec = 0;
+    const uint64_t o_dst = o_rrec + m * sizeof(RankRec);
+    const uint64_t o_pos = o_dst + scan_align16(m * 8);
+    const uint64_t o_rid = o_pos + scan_align16(m * 4);
+    const uint64_t o_oidx = o_rid + scan_align16(m * 4);
+    const uint64_t o_smap = o_oidx + max_entries * 16;
+    const uint64_t o_rido = o_smap + scan_align16(max_entries * 8);
+    const uint64_t scratch = o_rido + scan_align16(max_entries * 4);
+
+    hipStream_t s = rd->stream;
+    int rc = DBEEL_OK;
+    float ms[5] = {};
+    size_t t1 = 0, t2 = 0;
+    RankRec* d_rrec = nullptr;
+    uint64_t* d_dst = nullptr;
+    uint32_t* d_pos = nullptr;
+    uint32_t* d_rid = nullptr;
+    uint8_t* d_oidx = nullptr;
+    uint64_t* d_smap = nullptr;
+    uint32_t* d_rido = nullptr;
+    uint64_t taken = 0, bytes = 0, next = 0;
+
+#define SCAN_CHECK(call)                                                    \
+    do {                                                                    \
+        hipError_t _e = (call);                                             \
+        if (_e != hipSuccess) {                                             \
+            set_err("%s failed: %s", #call, hipGetErrorString(_e));         \
+            rc = (_e == hipErrorOutOfMemory) ? DBEEL_ERR_OOM                \
+                                             : DBEEL_ERR_HIP;               \
+            goto done;                                                      \
+        }                                                                   \
+    } while (0)
+
+    SCAN_CHECK(hipSetDevice(rd->device));
+    SCAN_CHECK(reader_reserve((void**)&rd->d_scan, &rd->scan_cap, scratch));
+    SCAN_CHECK(reader_reserve((void**)&rd->d_page, &rd->page_cap,
+                              scan_align16(cap ? cap : 16)));
+    /* sized for the smallest copy-window variant (8 KiB) */
+    SCAN_CHECK(reader_reserve((void**)&rd->d_scanwin, &rd->scanwin_cap,
+                              (cap / 8192 + 2) * sizeof(uint32_t)));
+    d_rrec = (RankRec*)(rd->d_scan + o_rrec);
+    d_dst = (uint64_t*)(rd->d_scan + o_dst);
+    d_pos = (uint32_t*)(rd->d_scan + o_pos);
+    d_rid = (uint32_t*)(rd->d_scan + o_rid);
+    d_oidx = rd->d_scan + o_oidx;
+    d_smap = (uint64_t*)(rd->d_scan + o_smap);
+    d_rido = (uint32_t*)(rd->d_scan + o_rido);
+    (void)rocprim::exclusive_scan(
+        nullptr, t1, rocprim::make_transform_iterator(d_rrec, RankRecSize{}),
+        d_dst, (uint64_t)0, m, rocprim::plus<uint64_t>(), s);
+    (void)rocprim::exclusive_scan(
+        nullptr, t2, rocprim::make_transform_iterator(d_rrec, RankRecFlag{}),
+        d_pos, (uint32_t)0, m, rocprim::plus<uint32_t>(), s);
+    if (t2 > t1) t1 = t2;
+    SCAN_CHECK(reader_reserve(&rd->d_scantmp, &rd->scantmp_cap, t1 ? t1 : 1));
+
+    SCAN_CHECK(hipEventRecord(rd->ev[0], s));
+    hipLaunchKernelGGL(k_reader_scan_flag, dim3(pick_grid(m, 256)), dim3(256),
+                       0, s, D, sc->win, sc->cursor, m, sc->d_ranges,
+                       sc->d_ranges + sc->n_ranges, sc->n_ranges, d_rrec,
+                       d_rid);
+    SCAN_CHECK(hipEventRecord(rd->ev[1], s));
+    t2 = t1;
+    SCAN_CHECK(rocprim::exclusive_scan(
+        rd->d_scantmp, t2,
+        rocprim::make_transform_iterator(d_rrec, RankRecSize{}), d_dst,
+        (uint64_t)0, m, rocprim::plus<uint64_t>(), s));
+    t2 = t1;
+    SCAN_CHECK(rocprim::exclusive_scan(
+        rd->d_scantmp, t2,
+        rocprim::make_transform_iterator(d_rrec, RankRecFlag{}), d_pos,
+        (uint32_t)0, m, rocprim::plus<uint32_t>(), s));
+    hipLaunchKernelGGL(k_reader_scan_emit, dim3(pick_grid(m, 256)), dim3(256),
+                       0, s, D, d_rrec, d_rid, d_dst, d_pos, m,
+                       (uint64_t)data_cap, max_entries, d_oidx, d_smap,
+                       d_rido, rd->d_scantot);
+    SCAN_CHECK(hipEventRecord(rd->ev[2], s));
+    {
+        /* the copy's grid comes from an upper bound on the page's bytes,
+         * its geometry from the tables' average entry size */
+        const uint64_t avg = D.total ? resident / D.total : 0;
+        launch_copy(s, d_oidx, d_smap, rd->d_scanwin, &rd->d_scantot->st,
+                    avg ? (cap + avg - 1) / avg : 0, cap, rd->d_page);
+    }
+    SCAN_CHECK(hipEventRecord(rd->ev[3], s));
+    SCAN_CHECK(hipMemcpyAsync(rd->h_scantot, rd->d_scantot,
+                              sizeof(ScanPageTotals), hipMemcpyDeviceToHost,
+                              s));
+    SCAN_CHECK(hipStreamSynchronize(s));
+    SCAN_CHECK(hipGetLastError());
+    taken = rd->h_scantot->st.n_surv;
+    bytes = rd->h_scantot->st.total_out;
+    next = rd->h_scantot->next;
+    if (taken > max_entries || bytes > cap || next > m) {
+        set_err("reader_scan_next: inconsistent page totals");
+        rc = DBEEL_ERR_HIP;
+        goto done;
+    }
+    if (taken == 0 && next < m) {
+        /* the first survivor alone exceeds data_cap (index_cap holds at
+         * least one record): ItemTooLarge, cursor untouched */
+        page->needed = rd->h_scantot->next_full;
+        set_err("reader_scan_next: entry of %llu bytes does not fit the "
+                "%zu-byte page buffer",
+                (unsigned long long)page->needed, data_cap);
+        rc = DBEEL_ERR_ITEM_TOO_LARGE;
+        goto done;
+    }
+    SCAN_CHECK(hipEventRecord(rd->ev[4], s));
+    if (taken) {
+        SCAN_CHECK(hipMemcpyAsync(data, rd->d_page, bytes,
+                                  hipMemcpyDeviceToHost, s));
+        SCAN_CHECK(hipMemcpyAsync(index, d_oidx, taken * 16,
+                                  hipMemcpyDeviceToHost, s));
+        if (sc->n_ranges && range_ids)
+            SCAN_CHECK(hipMemcpyAsync(range_ids, d_rido, taken * 4,
+                                      hipMemcpyDeviceToHost, s));
+    }
+    SCAN_CHECK(hipEventRecord(rd->ev[5], s));
+    SCAN_CHECK(hipStreamSynchronize(s));
+    SCAN_CHECK(hipGetLastError());
+    for (int i = 0; i < 5; i++)
+        SCAN_CHECK(hipEventElapsedTime(&ms[i], rd->ev[i], rd->ev[i + 1]));
+    sc->cursor += next;
+    page->data_len = bytes;
+    page->n_entries = taken;
+    page->candidates = next;
+    page->done = sc->cursor == sc->total;
+    page->flag_ms = ms[0];
+    page->emit_ms = ms[1];
+    page->copy_ms = ms[2];
+    page->d2h_ms = ms[4];
+done:
+    /* nothing of this page may still be in flight into the caller's
+     * buffers or the shared scratch */
+    if (rc != DBEEL_OK) (void)hipStreamSynchronize(s);
+    return rc;
+#undef SCAN_CHECK
 }
 
 extern "C" int dbeel_gpu_compact_timed(const dbeel_run_view* runs,

@@ -11,6 +11,8 @@ import os
 
 import numpy as np
 
+from .format import INDEX_DTYPE
+
 _DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_DIR, "libdbeel_gpu.so")
 
@@ -483,8 +485,116 @@ def _load_reader() -> ctypes.CDLL:
         lib.dbeel_gpu_reader_compact_abort.argtypes = [ctypes.c_void_p]
         lib.dbeel_gpu_bloom_free.restype = None
         lib.dbeel_gpu_bloom_free.argtypes = [ctypes.POINTER(ctypes.c_uint8)]
+        lib.dbeel_gpu_reader_scan_begin.restype = ctypes.c_int
+        lib.dbeel_gpu_reader_scan_begin.argtypes = [
+            ctypes.c_void_p,
+            ctypes.POINTER(ctypes.c_uint8), ctypes.c_size_t,
+            ctypes.POINTER(ctypes.c_uint8), ctypes.c_size_t,
+            ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
+            ctypes.c_size_t, ctypes.c_uint64,
+            ctypes.POINTER(ctypes.c_void_p),
+        ]
+        lib.dbeel_gpu_reader_scan_next.restype = ctypes.c_int
+        lib.dbeel_gpu_reader_scan_next.argtypes = [
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+            ctypes.POINTER(ScanPage),
+        ]
+        lib.dbeel_gpu_reader_scan_end.restype = None
+        lib.dbeel_gpu_reader_scan_end.argtypes = [ctypes.c_void_p]
         lib._reader_ready = True
     return lib
+
+
+class ScanPage(ctypes.Structure):
+    """dbeel_scan_page."""
+    _fields_ = [
+        ("data_len", ctypes.c_uint64),
+        ("n_entries", ctypes.c_uint64),
+        ("candidates", ctypes.c_uint64),
+        ("needed", ctypes.c_uint64),
+        ("done", ctypes.c_int),
+        ("flag_ms", ctypes.c_double),
+        ("emit_ms", ctypes.c_double),
+        ("copy_ms", ctypes.c_double),
+        ("d2h_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class ReaderScan:
+    """One open paged scan of a Reader (dbeel_gpu_reader_scan_*): next()
+    fills caller-owned numpy buffers with the next page. Made by
+    Reader.scan_open(); ended by close(), or by closing the reader."""
+
+    def __init__(self, reader: "Reader", start_key, end_key, hash_ranges,
+                 max_candidates: int):
+        if not reader._h:
+            raise ValueError("reader is closed")
+        self._reader = reader
+        self._lib = reader._lib
+        self._h = None
+
+        def _kb(b):
+            if b is None:
+                return None, 0, None
+            a = np.frombuffer(bytes(b) or b"\0", dtype=np.uint8)
+            return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), len(b), a
+
+        sp, sl, sa = _kb(start_key)
+        ep, el, ea = _kb(end_key)
+        self.n_ranges = len(hash_ranges) if hash_ranges else 0
+        rsp = rep = None
+        if self.n_ranges:
+            rs = np.array([r[0] for r in hash_ranges], dtype=np.uint32)
+            re_ = np.array([r[1] for r in hash_ranges], dtype=np.uint32)
+            rsp = rs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+            rep = re_.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+        h = ctypes.c_void_p()
+        rc = self._lib.dbeel_gpu_reader_scan_begin(
+            reader._h, sp, sl, ep, el, rsp, rep, self.n_ranges,
+            int(max_candidates), ctypes.byref(h))
+        del sa, ea  # begin has copied the bounds and ranges to the device
+        if rc != 0:
+            raise DbeelGpuError(rc, self._lib.dbeel_gpu_last_error().decode())
+        self._h = h
+        reader._scans.append(self)
+
+    def next(self, data: np.ndarray, index: np.ndarray, range_ids=None):
+        """Fill data (u8) / index (u8, 16 B per record) / range_ids (u32,
+        one slot per index record, or None) with the next page. Returns the
+        dbeel_scan_page as a dict. A first entry larger than data raises
+        DbeelGpuError with code 3 and .page["needed"] set; the scan stays
+        where it was, so next() may be called again with a larger buffer."""
+        if not self._h:
+            raise ValueError("scan is closed")
+        if range_ids is not None and range_ids.nbytes // 4 < index.nbytes // 16:
+            raise ValueError("range_ids needs one slot per index record")
+        pg = ScanPage()
+        rc = self._lib.dbeel_gpu_reader_scan_next(
+            self._h, data.ctypes.data, data.nbytes, index.ctypes.data,
+            index.nbytes,
+            None if range_ids is None else range_ids.ctypes.data,
+            ctypes.byref(pg))
+        if rc != 0:
+            err = DbeelGpuError(rc, self._lib.dbeel_gpu_last_error().decode())
+            err.page = pg.as_dict()
+            raise err
+        return pg.as_dict()
+
+    def close(self):
+        if self._h:
+            self._lib.dbeel_gpu_reader_scan_end(self._h)
+            self._h = None
+            self._reader._scans.remove(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 class Reader:
@@ -503,6 +613,7 @@ class Reader:
     def __init__(self, runs, blooms=None, device: int = 0):
         self._lib = _load_reader()
         self._h = None
+        self._scans = []  # open ReaderScans; close() ends them
         views, keepalive = _views(runs)
         bviews = None
         if blooms is not None:
@@ -531,6 +642,7 @@ class Reader:
         self = cls.__new__(cls)
         self._lib = _load_reader()
         self._h = handle
+        self._scans = []
         return self
 
     @property
@@ -664,8 +776,89 @@ class Reader:
         return [None if r < 0 else blob[off[q] : off[q + 1]]
                 for q, r in enumerate(hits["run"].tolist())]
 
+    def scan_open(self, start_key=None, end_key=None, hash_ranges=None,
+                  max_candidates: int = 0) -> ReaderScan:
+        """Begin a paged scan (engine.scan's filters) over the runs held;
+        see ReaderScan.next."""
+        return ReaderScan(self, start_key, end_key, hash_ranges,
+                          max_candidates)
+
+    def scan_pages(self, start_key=None, end_key=None, hash_ranges=None,
+                   page_bytes: int = 64 << 20, page_entries: int = 1 << 20,
+                   max_candidates: int = 0, pinned: bool = False):
+        """Paged migration scan over the resident runs: a generator of
+        (data, index, n, range_ids) numpy VIEWS of one reused pair of
+        buffers (copy what must outlive the next page). Every page is
+        shaped like a run file — index offsets start at 0 — and holds at
+        most page_bytes of entries and page_entries records; pages may be
+        short or empty. range_ids[p] is the first hash range matching entry
+        p (None without hash_ranges). Filters and yield order are
+        engine.scan's; the pages concatenated are its result. pinned=True
+        page-locks the buffers for the scan's lifetime. An entry larger
+        than page_bytes raises DbeelGpuError (code 3, .page["needed"])."""
+        data = np.empty(page_bytes, dtype=np.uint8)
+        index = np.empty(page_entries * 16, dtype=np.uint8)
+        rid = (np.empty(page_entries, dtype=np.uint32)
+               if hash_ranges else None)
+        bufs = [b for b in (data, index, rid) if b is not None]
+        done_pin = []
+        sc = None
+        try:
+            if pinned:
+                for b in bufs:
+                    pin_host(b)
+                    done_pin.append(b)
+            sc = self.scan_open(start_key, end_key, hash_ranges,
+                                max_candidates)
+            while True:
+                pg = sc.next(data, index, rid)
+                n = pg["n_entries"]
+                yield (data[:pg["data_len"]], index[:n * 16], n,
+                       None if rid is None else rid[:n])
+                if pg["done"]:
+                    break
+        finally:
+            if sc is not None:
+                sc.close()
+            for b in done_pin:
+                unpin_host(b)
+
+    def scan(self, start_key=None, end_key=None, hash_ranges=None,
+             page_bytes: int = 64 << 20, page_entries: int = 1 << 20,
+             max_candidates: int = 0, pinned: bool = False,
+             return_range_ids: bool = False):
+        """engine.scan over the resident runs: (data_bytes, index_bytes, n)
+        with the pages' index offsets rebased into one run file; with
+        return_range_ids also the u32 array of first matching ranges."""
+        datas, indexes, rids = [], [], []
+        off = 0
+        total = 0
+        for d, x, n, rid in self.scan_pages(
+                start_key, end_key, hash_ranges, page_bytes, page_entries,
+                max_candidates, pinned):
+            if not n:
+                continue
+            rec = x.view(INDEX_DTYPE).copy()
+            rec["offset"] += off
+            indexes.append(rec.tobytes())
+            datas.append(d.tobytes())
+            if rid is not None:
+                rids.append(rid.copy())
+            off += len(d)
+            total += n
+        out = (b"".join(datas), b"".join(indexes), total)
+        if return_range_ids:
+            ids = (np.concatenate(rids) if rids
+                   else np.zeros(0, dtype=np.uint32))
+            return out + (ids,)
+        return out
+
     def close(self):
         if getattr(self, "_h", None):
+            # reader_close ends the scans still open: drop their handles
+            for sc in self._scans:
+                sc._h = None
+            self._scans = []
             self._lib.dbeel_gpu_reader_close(self._h)
             self._h = None
 

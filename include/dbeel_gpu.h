@@ -208,7 +208,7 @@ int dbeel_gpu_reader_get(dbeel_gpu_reader* reader, const uint8_t* keys,
                          dbeel_get_result* out,
                          dbeel_get_stats* stats /* may be NULL */);
 void dbeel_gpu_get_result_free(dbeel_get_result* r);
-/* Frees the reader; a pending compaction is aborted. */
+/* Frees the reader; a pending compaction is aborted, open scans are ended. */
 void dbeel_gpu_reader_close(dbeel_gpu_reader* reader);
 
 /* ---- Live reader: the shared sstable list ----
@@ -272,6 +272,88 @@ int dbeel_gpu_reader_compact_begin(dbeel_gpu_reader* reader,
         dbeel_reader_compact_stats* stats /* may be NULL */);
 int  dbeel_gpu_reader_compact_commit(dbeel_gpu_reader* reader, size_t out_pos);
 void dbeel_gpu_reader_compact_abort(dbeel_gpu_reader* reader);
+
+/* ---- Paged migration scan over the resident tables ----
+ * dbeel_gpu_scan (below) for runs the reader already holds: the AsyncIter
+ * analogue (lsm_tree.rs:141-282) iterating the shared sstable list
+ * (`tree.sstables.borrow().clone()`, lsm_tree.rs:177) and feeding migration
+ * (tasks/migration.rs:62-131) page by page, straight into caller memory.
+ * No run is uploaded, no compaction scratch is allocated, and no entry
+ * outside the key range is ever loaded.
+ *
+ * Filter semantics are exactly dbeel_gpu_scan's: key range
+ * [start_key, end_key) with a NULL bound unbounded (a non-NULL zero-length
+ * end_key keeps nothing), murmur3_32 seed-0 hash ranges with between_cmp's
+ * wrapped case, no dedup, no tombstone filter; yield order = table position
+ * ascending, key order within a table. The concatenation of all pages
+ * (index offsets rebased) is byte-identical to dbeel_gpu_scan over the same
+ * runs and filters, for every choice of caps and max_candidates.
+ *
+ * begin: bisects each table's resident prefix array for
+ * lower_bound(start_key) and lower_bound(end_key) (equal-prefix stretches
+ * are settled by bisection with full key compares, never a walk) — one
+ * small kernel, one sync, one small D2H. The CANDIDATES are the
+ * concatenation over tables of the entries between the two bounds; the
+ * scan's cursor is a position in that space. max_candidates bounds how many
+ * candidates one page examines (0 = default 2^20; values above 2^31 are
+ * clamped to 2^31); per-page device scratch is about 60 B per candidate,
+ * belongs to the reader and is reused, like a device page buffer of
+ * min(data_cap, resident data bytes); neither counts in table_bytes.
+ *
+ * next: examines the next min(remaining, max_candidates) candidates.
+ * Those passing the hash filter are survivors; the page takes the longest
+ * prefix of survivors with summed full_size <= data_cap and count <=
+ * index_cap/16, and writes their bytes to data, their 16-B index records
+ * (offsets from 0 in every page, like a run file holding the page) to
+ * index and, when n_ranges != 0 and range_ids is not NULL, the index of
+ * the FIRST range matching each entry's hash (`position`,
+ * migration.rs:97-104) to range_ids. The cursor moves to the first
+ * survivor not taken, or past the window when all were taken. A page may
+ * be short or empty with done = 0: loop until done. If the first survivor
+ * is larger than data_cap the call returns DBEEL_ERR_ITEM_TOO_LARGE, sets
+ * page->needed to its full_size and leaves the cursor where it was: call
+ * again with a larger buffer. Copies are hipMemcpyAsync on the reader's
+ * stream (true async DMA when the buffers are registered with
+ * dbeel_gpu_pin_host); the engine allocates no host memory for results.
+ * Arguments are validated before any device call: a NULL scan, page, data
+ * or index, data_cap == 0 or index_cap < 16 is DBEEL_ERR_INVALID_ARG.
+ *
+ * Liveness: a scan sees the list as dbeel_gpu_reader_get does (a pending
+ * compaction is invisible). insert_run and compact_commit change the list
+ * and invalidate every open scan: next then returns DBEEL_ERR_INVALID_ARG
+ * ("stale scan") and the caller restarts; compact_begin / compact_abort do
+ * not. (Divergence: the reference's iterator keeps its cloned list alive,
+ * lsm_tree.rs:175-177.) Any number of scans may be open on a reader, under
+ * the same one-thread-per-reader contract; dbeel_gpu_reader_close ends the
+ * scans still open, after which their handles must not be used. */
+typedef struct dbeel_gpu_reader_scan dbeel_gpu_reader_scan;
+
+typedef struct {
+    uint64_t data_len;     /* bytes written to data                         */
+    uint64_t n_entries;    /* index records written (16 B each)             */
+    uint64_t candidates;   /* in-key-range entries examined by this page    */
+    uint64_t needed;       /* on DBEEL_ERR_ITEM_TOO_LARGE: full_size of the
+                              entry that did not fit; else 0                */
+    int      done;         /* 1 = nothing left after this page              */
+    double   flag_ms, emit_ms, copy_ms, d2h_ms; /* HIP events, reader stream:
+                              flag kernel | scans + emit | winmap + copy |
+                              copies into the caller's buffers             */
+} dbeel_scan_page;
+
+int  dbeel_gpu_reader_scan_begin(dbeel_gpu_reader* reader,
+        const uint8_t* start_key, size_t start_key_len,
+        const uint8_t* end_key,   size_t end_key_len,
+        const uint32_t* range_starts, const uint32_t* range_ends,
+        size_t n_ranges,
+        uint64_t max_candidates /* per page; 0 = default 2^20 */,
+        dbeel_gpu_reader_scan** out);
+int  dbeel_gpu_reader_scan_next(dbeel_gpu_reader_scan* scan,
+        uint8_t* data, size_t data_cap,
+        uint8_t* index, size_t index_cap,        /* bytes */
+        uint32_t* range_ids /* NULL or index_cap/16 slots */,
+        dbeel_scan_page* page);
+/* Frees the scan; NULL is a no-op. */
+void dbeel_gpu_reader_scan_end(dbeel_gpu_reader_scan* scan);
 
 /* ---- Run encoder (the memtable-flush path) ----
  * Encodes an already-sorted (key, value, timestamp) stream into a run:

@@ -137,15 +137,16 @@ def reader_trial(rng, runs, device):
             queries.append(bytes(rng.integers(
                 0, 256, int(rng.integers(0, 40)), dtype=np.uint8)))
     exp = [model[k][1] if k in model else None for k in queries]
-    live_why = None
+    live_why = scan_why = None
     with Reader(runs, blooms=blooms, device=device) as rd:
         got = rd.get(queries)
         _, _, _, st = rd.get_raw(queries)
-        if got == exp:
+        scan_why = paged_scan_step(rng, rd, runs, stored)
+        if got == exp and not scan_why:
             live_why = live_reader_step(rng, rd, runs, blooms, queries,
                                         device)
-    if live_why:
-        return live_why
+    if scan_why or live_why:
+        return scan_why or live_why
     if got != exp:
         bad = next(i for i, (g, e) in enumerate(zip(got, exp)) if g != e)
         return f"key {queries[bad].hex()} got {got[bad]} want {exp[bad]}"
@@ -160,6 +161,46 @@ def reader_trial(rng, runs, device):
         for e in parse_run(d, i)[::17]:
             if not lsm.bloom_contains(blooms[r], e.key):
                 return f"filter of run {r} misses stored key {e.key.hex()}"
+    return None
+
+
+def paged_scan_step(rng, rd, runs, stored):
+    """One paged scan of the open reader with random bounds (stored keys,
+    their neighbours, random bytes), hash ranges, page capacities and
+    candidate window, against the AsyncIter model."""
+    sys.path.insert(0, os.path.join(
+        os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    from pymm3 import between_cmp, murmur3_32, scan_model
+
+    from dbeel_amd.format import parse_run
+
+    kw = random_scan_filter(rng)
+    for side in ("start_key", "end_key"):
+        if stored and rng.random() < 0.5:
+            k = stored[int(rng.integers(0, len(stored)))]
+            pick = rng.random()
+            kw[side] = (k if pick < 0.5 else k + b"\x00" if pick < 0.75
+                        else k[: len(k) // 2])
+    md, mi, mn = scan_model(runs, **kw)
+    biggest = max([32] + [len(d) for d, _ in runs])
+    paging = dict(
+        # never below the largest entry: 32 + 128 B key + 299 B value
+        page_bytes=int(rng.integers(459, max(460, biggest))),
+        page_entries=int(rng.integers(1, 700)),
+        max_candidates=int(rng.choice([0, 1, 2, 63, 64, 65, 1000])),
+        pinned=bool(rng.random() < 0.2))
+    if paging["max_candidates"] == 1 and sum(len(i) for _, i in runs) > 16000:
+        paging["max_candidates"] = 17  # keep the page count bounded
+    gd, gi, gn, ids = rd.scan(return_range_ids=True, **kw, **paging)
+    if (gd, gi, gn) != (md, mi, mn):
+        return f"paged scan {kw} {paging}: n {gn} vs {mn}"
+    ranges = kw.get("hash_ranges")
+    if ranges:
+        want = [next(j for j, (s, t) in enumerate(ranges)
+                     if between_cmp(murmur3_32(e.key, 0), s, t))
+                for e in parse_run(md, mi)]
+        if ids.tolist() != want:
+            return f"paged scan {kw} {paging}: range ids differ"
     return None
 
 

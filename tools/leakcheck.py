@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Device-memory stability check: churn job create/run/fetch/destroy,
 streamed ingests (each creates ~per-chunk HIP events), batched jobs,
-scans, sliced compactions and resident readers (open / get x N / insert /
-compact begin + abort + commit / close), reporting hipMemGetInfo drift. A leak in
+scans, sliced compactions and resident readers (open / get x N / paged
+scans begin + next + end, one left for close to end / insert / compact
+begin + abort + commit / close), reporting hipMemGetInfo drift. A leak in
 any path shows as monotonically shrinking free memory.
 
     python tools/leakcheck.py --iters 40
@@ -91,6 +92,20 @@ def main():
                         device=0) as rd:
                 for n in (10, 4000, 100, 20_000):
                     rd.get(probe_keys[:n])
+                # paged scans: begin / next x N / end with growing and
+                # shrinking windows and page buffers (scratch regrowth), a
+                # pinned one, and one abandoned mid-way for close to end
+                for pb, pe, mc in ((1 << 16, 100, 1000), (1 << 22, 50_000, 0),
+                                   (1 << 14, 7, 64)):
+                    for page in rd.scan_pages(hash_ranges=[(0, 1 << 30)],
+                                              page_bytes=pb, page_entries=pe,
+                                              max_candidates=mc):
+                        if mc == 64 and page[2]:
+                            break  # generator closed early: scan_end
+                rd.scan(start_key=b"\x40", page_bytes=1 << 20, pinned=True)
+                abandoned = rd.scan_open(end_key=b"\xc0", max_candidates=500)
+                abandoned.next(np.empty(1 << 16, dtype=np.uint8),
+                               np.empty(16 * 64, dtype=np.uint8))
                 # live updates: insert / compact / abort / commit — every
                 # table they allocate is freed by the swap or by close
                 rd.insert_run(2, runs2[0])
