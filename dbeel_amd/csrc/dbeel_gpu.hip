@@ -96,6 +96,10 @@ extern "C" __attribute__((visibility("hidden"))) void dbeel_set_last_error(
     set_err("%s", msg);
 }
 
+/* The one check macro: a failed HIP call sets the error text and returns
+ * DBEEL_ERR_OOM / DBEEL_ERR_HIP from the enclosing function. What has to
+ * be undone on the way out is the function's business, declared once as a
+ * ScopeGuard. */
 #define HIP_CHECK(call)                                                     \
     do {                                                                    \
         hipError_t _e = (call);                                             \
@@ -106,6 +110,45 @@ extern "C" __attribute__((visibility("hidden"))) void dbeel_set_last_error(
                                                : DBEEL_ERR_HIP;             \
         }                                                                   \
     } while (0)
+
+/* Runs f when the scope ends, on every path out of it, unless dismissed. */
+template <typename F>
+struct ScopeGuard {
+    F f;
+    bool armed = true;
+    explicit ScopeGuard(F fn) : f(fn) {}
+    ScopeGuard(const ScopeGuard&) = delete;
+    ScopeGuard& operator=(const ScopeGuard&) = delete;
+    ~ScopeGuard() {
+        if (armed) f();
+    }
+    void dismiss() { armed = false; }
+};
+
+/* The device argument of every entry point: there is no CPU fallback. */
+static int check_device_arg(int device) {
+    if (device >= 0) return DBEEL_OK;
+    set_err("device must be >= 0 (no CPU fallback in the product library; "
+            "the CPU restatement lives in oracle/liboracle.so and is test "
+            "infrastructure only)");
+    return DBEEL_ERR_INVALID_ARG;
+}
+
+/* Makes `device` the calling thread's HIP device: DBEEL_ERR_INVALID_ARG
+ * for a negative one, DBEEL_ERR_NO_GPU when HIP cannot provide it. */
+static int select_device(int device) {
+    int rc = check_device_arg(device);
+    if (rc) return rc;
+    int ndev = 0;
+    hipError_t de = hipGetDeviceCount(&ndev);
+    if (de != hipSuccess || device >= ndev) {
+        set_err("no usable HIP device %d (count=%d, %s)", device, ndev,
+                hipGetErrorString(de));
+        return DBEEL_ERR_NO_GPU;
+    }
+    HIP_CHECK(hipSetDevice(device));
+    return DBEEL_OK;
+}
 
 /* ------------------------------------------------------------------ */
 /* Device-side format view                                            */
@@ -142,16 +185,20 @@ __device__ __forceinline__ uint32_t ld_u32(const uint8_t* p) {
     return v;
 }
 
-/* Loads index record + key view. Returns false on corrupt record. */
+/* Loads index record + key view. Returns false on a corrupt record, and
+ * then e.raw / e.key are not set: nothing may be read through them. This
+ * is the only bounds check there is — off and full_size come from the
+ * input, so it is written so that no sum of them can wrap. */
 __device__ __forceinline__ bool load_entry(const RunsDesc& R, int r,
                                            uint64_t i, EView& e) {
     const uint8_t* rec = R.index[r] + i * 16;
     e.off = ld_u64(rec);
     e.key_size = ld_u32(rec + 8);
     e.full_size = ld_u32(rec + 12);
+    const uint64_t dlen = R.data_len[r];
     if (e.key_size < 8 || e.full_size < 32 ||
         (uint64_t)e.key_size + 24 > e.full_size ||
-        e.off + e.full_size > R.data_len[r])
+        e.off > dlen || e.full_size > dlen - e.off)
         return false;
     e.raw = R.data[r] + e.off;
     e.klen = e.key_size - 8;
@@ -197,20 +244,6 @@ __device__ __forceinline__ void load_ts(const EView& e, uint64_t& lo,
     hi = h;
 }
 
-/* Full total order: (key, timestamp, run index) — lsm_tree.rs:52-71. */
-__device__ __forceinline__ int cmp_full(const EView& a, int ra,
-                                        const EView& b, int rb) {
-    int c = cmp_keys(a.key, a.klen, b.key, b.klen);
-    if (c) return c;
-    uint64_t alo, blo;
-    int64_t ahi, bhi;
-    load_ts(a, alo, ahi);
-    load_ts(b, blo, bhi);
-    if (ahi != bhi) return ahi < bhi ? -1 : 1;
-    if (alo != blo) return alo < blo ? -1 : 1;
-    return ra < rb ? -1 : (ra > rb ? 1 : 0);
-}
-
 /* ------------------------------------------------------------------ */
 /* Kernels                                                            */
 /* ------------------------------------------------------------------ */
@@ -232,6 +265,85 @@ __device__ __forceinline__ uint64_t key_prefix(const uint8_t* key,
         for (uint64_t j = 0; j < klen; j++) v |= (uint64_t)key[j] << (8 * j);
     }
     return __builtin_bswap64(v);
+}
+
+/* The run that owns global entry g (<= 64 runs: linear scan on the cached
+ * desc). */
+__device__ __forceinline__ int run_of(const RunsDesc& R, uint64_t g) {
+    int r = 0;
+    while (r + 1 < R.n_runs && g >= R.entry_base[r + 1]) r++;
+    return r;
+}
+
+/* What k_prepare and k_reader_prepare ask of an entry that load_entry
+ * accepted: the bincode length fields agree with the index record
+ * (read_next_entry, lsm_tree.rs:1158-70), and the successor's offset is
+ * monotone and does not overlap (EntryWriter appends —
+ * entry_writer.rs:71-98; the streamed-ingest chunking relies on it). */
+__device__ __forceinline__ bool entry_consistent(const RunsDesc& R, int r,
+                                                 uint64_t i,
+                                                 const EView& e) {
+    if (ld_u64(e.raw) != e.klen ||
+        ld_u64(e.raw + 8 + e.klen) != (uint64_t)e.full_size - 32 - e.klen)
+        return false;
+    return i + 1 >= R.count[r] ||
+           e.off + e.full_size <= ld_u64(R.index[r] + (i + 1) * 16);
+}
+
+/* ---- Search inside one run: bisect the dense prefix array, then settle
+ * the equal-prefix stretch (zero padding, bytes past 8, length) with full
+ * key compares on the blob — never a walk. ---- */
+
+/* First i in [0, n) with P[i] >= qp; n when there is none. */
+__device__ __forceinline__ uint64_t pfx_lower_bound(const uint64_t* P,
+                                                    uint64_t n,
+                                                    uint64_t qp) {
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+        uint64_t mid = (lo + hi) >> 1;
+        if (P[mid] < qp)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+/* First i in [lo, n) with P[i] > qp; n when there is none. */
+__device__ __forceinline__ uint64_t pfx_upper_bound(const uint64_t* P,
+                                                    uint64_t lo, uint64_t n,
+                                                    uint64_t qp) {
+    uint64_t hi = n;
+    while (lo < hi) {
+        uint64_t mid = (lo + hi) >> 1;
+        if (P[mid] <= qp)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+/* First entry in [lo, hi) of run r whose key is >= (key, klen); hi when
+ * there is none. A record that fails to load narrows from above: on
+ * corrupt input the search degrades safely. */
+__device__ __forceinline__ uint64_t blob_lower_bound(const RunsDesc& R, int r,
+                                                     uint64_t lo, uint64_t hi,
+                                                     const uint8_t* key,
+                                                     uint64_t klen) {
+    while (lo < hi) {
+        uint64_t mid = (lo + hi) >> 1;
+        EView m;
+        if (!load_entry(R, r, mid, m)) {
+            hi = mid;
+            continue;
+        }
+        if (cmp_keys(m.key, m.klen, key, klen) < 0)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
 }
 
 /* Dense per-entry search record: the key's SUFFIX bytes (8..8+KB,
@@ -265,6 +377,24 @@ template <int KB> struct AuxT<KB, true> {
 static_assert(sizeof(AuxT<12, false>) == 16, "tier-0 aux must be 16B");
 static_assert(sizeof(AuxT<24, true>) == 48, "tier-1 aux must be 48B");
 static_assert(sizeof(AuxT<40, true>) == 64, "tier-2 aux must be 64B");
+
+/* Host-side tier dispatch: calls f with the <KB, TS> of a job's aux_kind
+ * (0: 16-B, 1: 48-B, 2: 64-B records) as compile-time constants, for the
+ * templated launches:
+ *   with_aux_tier(kind, [&](auto tier) {
+ *       using T = decltype(tier);  ... k_x<T::KB, T::TS> ... }); */
+template <int KB_, bool TS_> struct AuxTier {
+    static constexpr int KB = KB_;
+    static constexpr bool TS = TS_;
+    using Rec = AuxT<KB_, TS_>;
+};
+template <typename F> static void with_aux_tier(int kind, F&& f) {
+    switch (kind) {
+        case 0: f(AuxTier<12, false>{}); break;
+        case 1: f(AuxTier<24, true>{}); break;
+        case 2: f(AuxTier<40, true>{}); break;
+    }
+}
 
 /* Key-only compare of entries A=(rA,iA), B=(rB,iB) via suffix records.
  * PRECONDITION: pfx(A) == pfx(B) (every caller compares pfx first), so
@@ -448,9 +578,7 @@ __global__ void k_prepare(RunsDesc R, uint64_t g0, uint64_t g1,
     uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t g = g0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
          g < g1; g += stride) {
-        /* locate run (<= 64 runs: linear scan on cached desc) */
-        int r = 0;
-        while (r + 1 < R.n_runs && g >= R.entry_base[r + 1]) r++;
+        int r = run_of(R, g);
         uint64_t i = g - R.entry_base[r];
         EView e;
         if (!load_entry(R, r, i, e)) {
@@ -497,18 +625,7 @@ __global__ void k_prepare(RunsDesc R, uint64_t g0, uint64_t g1,
             }
         }
         aux[g] = a;
-        /* bincode field cross-check */
-        if (ld_u64(e.raw) != e.klen ||
-            ld_u64(e.raw + 8 + e.klen) != (uint64_t)e.full_size - 32 - e.klen)
-            atomicOr(err, DERR_CORRUPT);
-        /* entries within a run must not overlap and offsets must be
-         * monotone (EntryWriter appends — entry_writer.rs:71-98; the
-         * streamed-ingest chunking relies on this invariant) */
-        if (i + 1 < R.count[r]) {
-            uint64_t noff = ld_u64(R.index[r] + (i + 1) * 16);
-            if (e.off + e.full_size > noff)
-                atomicOr(err, DERR_CORRUPT);
-        }
+        if (!entry_consistent(R, r, i, e)) atomicOr(err, DERR_CORRUPT);
     }
 }
 
@@ -836,8 +953,7 @@ __global__ void k_rankreduce(RunsDesc R, const uint64_t* pfx,
     uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
          g < R.total; g += stride) {
-        int r = 0;
-        while (r + 1 < R.n_runs && g >= R.entry_base[r + 1]) r++;
+        int r = run_of(R, g);
         uint64_t i = g - R.entry_base[r];
         EView e;
         if (!load_entry(R, r, i, e)) {
@@ -904,6 +1020,25 @@ struct RankRecPacked {
                    : 0ull;
     }
 };
+
+/* The two-scan form: survivor byte offsets into dst_off, survivor
+ * positions into pos, for n records. rocPRIM's calling convention: with
+ * tmp == NULL nothing runs and tmp_bytes receives the scratch size the pair
+ * needs; otherwise tmp_bytes is the size of tmp. */
+static hipError_t survivor_scans(void* tmp, size_t& tmp_bytes,
+                                 const RankRec* rrec, uint64_t* dst_off,
+                                 uint32_t* pos, uint64_t n, hipStream_t s) {
+    size_t t1 = tmp_bytes, t2 = tmp_bytes;
+    hipError_t e = rocprim::exclusive_scan(
+        tmp, t1, rocprim::make_transform_iterator(rrec, RankRecSize{}),
+        dst_off, (uint64_t)0, n, rocprim::plus<uint64_t>(), s);
+    if (e == hipSuccess)
+        e = rocprim::exclusive_scan(
+            tmp, t2, rocprim::make_transform_iterator(rrec, RankRecFlag{}),
+            pos, (uint32_t)0, n, rocprim::plus<uint32_t>(), s);
+    if (!tmp) tmp_bytes = t1 > t2 ? t1 : t2;
+    return e;
+}
 
 /* The step's totals stay on the device: the emit thread that owns the
  * last rank derives them from its scan value and stores them here, and
@@ -1270,17 +1405,8 @@ extern "C" int dbeel_gpu_encode_run(uint64_t n_entries, const uint8_t* keys,
         return DBEEL_ERR_INVALID_ARG;
     }
     memset(out, 0, sizeof *out);
-    if (device < 0) {
-        set_err("device must be >= 0 (no CPU fallback)");
-        return DBEEL_ERR_INVALID_ARG;
-    }
-    int ndev = 0;
-    hipError_t de = hipGetDeviceCount(&ndev);
-    if (de != hipSuccess || device >= ndev) {
-        set_err("no usable HIP device %d", device);
-        return DBEEL_ERR_NO_GPU;
-    }
-    HIP_CHECK(hipSetDevice(device));
+    int rc = select_device(device);
+    if (rc) return rc;
     if (n_entries == 0) {
         out->data = (uint8_t*)malloc(1);
         out->index = (uint8_t*)malloc(1);
@@ -1306,95 +1432,78 @@ extern "C" int dbeel_gpu_encode_run(uint64_t n_entries, const uint8_t* keys,
              *d_doff = nullptr;
     void* d_tmp = nullptr;
     hipStream_t s = nullptr;
-    uint64_t total = 0;
-    int rc = DBEEL_OK;
     size_t tmp_bytes = 0;
+    /* guards run in reverse: the device side is released (hipFree waits
+     * for the stream) before a failed call's host buffers go */
+    ScopeGuard drop_out([&] { dbeel_gpu_result_free(out); });
+    ScopeGuard release([&] {
+        hipFree(d_keys);
+        hipFree(d_vals);
+        hipFree(d_ts);
+        hipFree(d_koff);
+        hipFree(d_voff);
+        hipFree(d_sizes);
+        hipFree(d_doff);
+        hipFree(d_tmp);
+        hipFree(d_outd);
+        hipFree(d_outi);
+        if (s) hipStreamDestroy(s);
+    });
 
-#define ENC_CHECK(call)                                                     \
-    do {                                                                    \
-        hipError_t _e = (call);                                             \
-        if (_e != hipSuccess) {                                             \
-            set_err("%s failed: %s", #call, hipGetErrorString(_e));         \
-            rc = (_e == hipErrorOutOfMemory) ? DBEEL_ERR_OOM                \
-                                             : DBEEL_ERR_HIP;               \
-            goto done;                                                      \
-        }                                                                   \
-    } while (0)
-
-    ENC_CHECK(hipStreamCreate(&s));
-    ENC_CHECK(hipMalloc(&d_keys, kbytes ? kbytes : 1));
-    ENC_CHECK(hipMalloc(&d_vals, vbytes ? vbytes : 1));
-    ENC_CHECK(hipMalloc(&d_ts, n * 16));
-    ENC_CHECK(hipMalloc(&d_koff, (n + 1) * 8));
-    ENC_CHECK(hipMalloc(&d_voff, (n + 1) * 8));
-    ENC_CHECK(hipMalloc(&d_sizes, n * 8));
-    ENC_CHECK(hipMalloc(&d_doff, n * 8));
-    ENC_CHECK(hipMemcpyAsync(d_keys, keys, kbytes ? kbytes : 1,
+    HIP_CHECK(hipStreamCreate(&s));
+    HIP_CHECK(hipMalloc(&d_keys, kbytes ? kbytes : 1));
+    HIP_CHECK(hipMalloc(&d_vals, vbytes ? vbytes : 1));
+    HIP_CHECK(hipMalloc(&d_ts, n * 16));
+    HIP_CHECK(hipMalloc(&d_koff, (n + 1) * 8));
+    HIP_CHECK(hipMalloc(&d_voff, (n + 1) * 8));
+    HIP_CHECK(hipMalloc(&d_sizes, n * 8));
+    HIP_CHECK(hipMalloc(&d_doff, n * 8));
+    HIP_CHECK(hipMemcpyAsync(d_keys, keys, kbytes ? kbytes : 1,
                              hipMemcpyHostToDevice, s));
-    ENC_CHECK(hipMemcpyAsync(d_vals, values, vbytes ? vbytes : 1,
+    HIP_CHECK(hipMemcpyAsync(d_vals, values, vbytes ? vbytes : 1,
                              hipMemcpyHostToDevice, s));
-    ENC_CHECK(hipMemcpyAsync(d_ts, timestamps, n * 16,
+    HIP_CHECK(hipMemcpyAsync(d_ts, timestamps, n * 16,
                              hipMemcpyHostToDevice, s));
-    ENC_CHECK(hipMemcpyAsync(d_koff, key_offsets, (n + 1) * 8,
+    HIP_CHECK(hipMemcpyAsync(d_koff, key_offsets, (n + 1) * 8,
                              hipMemcpyHostToDevice, s));
-    ENC_CHECK(hipMemcpyAsync(d_voff, value_offsets, (n + 1) * 8,
+    HIP_CHECK(hipMemcpyAsync(d_voff, value_offsets, (n + 1) * 8,
                              hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_encode_sizes, dim3(pick_grid(n, 256)), dim3(256), 0,
                        s, n, d_koff, d_voff, d_sizes);
-    (void)rocprim::exclusive_scan(nullptr, tmp_bytes, d_sizes, d_doff,
-                                  (uint64_t)0, n, rocprim::plus<uint64_t>(),
-                                  s);
-    ENC_CHECK(hipMalloc(&d_tmp, tmp_bytes));
-    (void)rocprim::exclusive_scan(d_tmp, tmp_bytes, d_sizes, d_doff,
-                                  (uint64_t)0, n, rocprim::plus<uint64_t>(),
-                                  s);
-    total = 32 * n + kbytes + vbytes; /* 32+klen+vlen per entry */
-    ENC_CHECK(hipMalloc(&d_outd, total));
-    ENC_CHECK(hipMalloc(&d_outi, n * 16));
+    HIP_CHECK(rocprim::exclusive_scan(nullptr, tmp_bytes, d_sizes, d_doff,
+                                      (uint64_t)0, n,
+                                      rocprim::plus<uint64_t>(), s));
+    HIP_CHECK(hipMalloc(&d_tmp, tmp_bytes));
+    HIP_CHECK(rocprim::exclusive_scan(d_tmp, tmp_bytes, d_sizes, d_doff,
+                                      (uint64_t)0, n,
+                                      rocprim::plus<uint64_t>(), s));
+    const uint64_t total = 32 * n + kbytes + vbytes; /* 32+klen+vlen each */
+    HIP_CHECK(hipMalloc(&d_outd, total));
+    HIP_CHECK(hipMalloc(&d_outi, n * 16));
     hipLaunchKernelGGL(k_encode_index, dim3(pick_grid(n, 256)), dim3(256), 0,
                        s, n, d_koff, d_doff, d_sizes, d_outi);
     hipLaunchKernelGGL(k_encode_data, dim3(pick_grid(n * 64, 256)), dim3(256),
                        0, s, n, d_keys, d_koff, d_vals, d_voff, d_ts, d_doff,
                        d_outd);
-    ENC_CHECK(hipStreamSynchronize(s));
-    ENC_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipGetLastError());
 
     out->data = (uint8_t*)malloc(total ? total : 1);
     out->index = (uint8_t*)malloc(n * 16);
     if (!out->data || !out->index) {
-        free(out->data);
-        free(out->index);
-        memset(out, 0, sizeof *out);
-        rc = DBEEL_ERR_OOM;
-        goto done;
+        set_err("host malloc failed");
+        return DBEEL_ERR_OOM;
     }
-    ENC_CHECK(hipMemcpyAsync(out->data, d_outd, total,
+    HIP_CHECK(hipMemcpyAsync(out->data, d_outd, total,
                              hipMemcpyDeviceToHost, s));
-    ENC_CHECK(hipMemcpyAsync(out->index, d_outi, n * 16,
+    HIP_CHECK(hipMemcpyAsync(out->index, d_outi, n * 16,
                              hipMemcpyDeviceToHost, s));
-    ENC_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipStreamSynchronize(s));
     out->data_len = total;
     out->index_len = n * 16;
     out->entries_written = n;
-done:
-    hipFree(d_keys);
-    hipFree(d_vals);
-    hipFree(d_ts);
-    hipFree(d_koff);
-    hipFree(d_voff);
-    hipFree(d_sizes);
-    hipFree(d_doff);
-    hipFree(d_tmp);
-    hipFree(d_outd);
-    hipFree(d_outi);
-    if (s) hipStreamDestroy(s);
-    if (rc != DBEEL_OK && out->data) {
-        free(out->data);
-        free(out->index);
-        memset(out, 0, sizeof *out);
-    }
-    return rc;
-#undef ENC_CHECK
+    drop_out.dismiss();
+    return DBEEL_OK;
 }
 
 /* ------------------------------------------------------------------ */
@@ -1416,8 +1525,7 @@ __global__ void k_maxks(RunsDesc R, uint32_t* out) {
     uint32_t m = 0;
     for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
          g < R.total; g += stride) {
-        int r = 0;
-        while (r + 1 < R.n_runs && g >= R.entry_base[r + 1]) r++;
+        int r = run_of(R, g);
         uint64_t i = g - R.entry_base[r];
         uint32_t ks = ld_u32(R.index[r] + i * 16 + 8);
         if (ks > m) m = ks;
@@ -1549,23 +1657,12 @@ static int job_create_impl(const dbeel_run_view* runs, size_t n_runs,
             return DBEEL_ERR_INVALID_ARG;
         }
     }
-    if (device < 0) {
-        set_err("device must be >= 0 (no CPU fallback in the product "
-                "library; the CPU restatement lives in oracle/liboracle.so "
-                "and is test infrastructure only)");
-        return DBEEL_ERR_INVALID_ARG;
-    }
-    int ndev = 0;
-    hipError_t de = hipGetDeviceCount(&ndev);
-    if (de != hipSuccess || device >= ndev) {
-        set_err("no usable HIP device %d (count=%d, %s)", device, ndev,
-                hipGetErrorString(de));
-        return DBEEL_ERR_NO_GPU;
-    }
-    HIP_CHECK(hipSetDevice(device));
+    rc = select_device(device);
+    if (rc) return rc;
 
     dbeel_gpu_job* job = new (std::nothrow) dbeel_gpu_job();
     if (!job) return DBEEL_ERR_OOM;
+    ScopeGuard drop_job([&] { dbeel_gpu_job_destroy(job); });
     job->device = device;
     job->borrowed = borrowed;
 
@@ -1579,65 +1676,44 @@ static int job_create_impl(const dbeel_run_view* runs, size_t n_runs,
     job->total_data_bytes = total_data;
     job->input_bytes = input_bytes;
 
-#define JOB_CHECK(call)                                                     \
-    do {                                                                    \
-        hipError_t _e = (call);                                             \
-        if (_e != hipSuccess) {                                             \
-            set_err("%s failed: %s", #call, hipGetErrorString(_e));         \
-            dbeel_gpu_job_destroy(job);                                     \
-            return (_e == hipErrorOutOfMemory) ? DBEEL_ERR_OOM              \
-                                               : DBEEL_ERR_HIP;             \
-        }                                                                   \
-    } while (0)
-
-    JOB_CHECK(hipStreamCreate(&job->stream));
-    for (int i = 0; i < 8; i++) JOB_CHECK(hipEventCreate(&job->ev[i]));
+    HIP_CHECK(hipStreamCreate(&job->stream));
+    for (int i = 0; i < 8; i++) HIP_CHECK(hipEventCreate(&job->ev[i]));
 
     /* +-16 B padding: the copy kernel's aligned-base loads may touch up
      * to 15 B before/after an entry's bytes */
     if (!borrowed)
-        JOB_CHECK(hipMalloc(&job->d_input,
+        HIP_CHECK(hipMalloc(&job->d_input,
                             (input_bytes ? input_bytes : 16) + 32));
     uint64_t n = total ? total : 1;
-    JOB_CHECK(hipMalloc(&job->d_rank, n * sizeof(RankRec)));
-    JOB_CHECK(hipMalloc(&job->d_dstoff, n * sizeof(uint64_t)));
-    JOB_CHECK(hipMalloc(&job->d_pos, n * sizeof(uint32_t)));
-    JOB_CHECK(hipMalloc(&job->d_outindex, n * 16));
-    JOB_CHECK(hipMalloc(&job->d_srcmap, n * sizeof(uint64_t)));
-    JOB_CHECK(hipMalloc(&job->d_outdata, total_data ? total_data : 16));
-    JOB_CHECK(hipMalloc(&job->d_err, 2 * sizeof(uint32_t)));
-    JOB_CHECK(hipMalloc(&job->d_pfx, n * sizeof(uint64_t)));
-    JOB_CHECK(hipMalloc(&job->d_tot, sizeof(StepTotals)));
-    JOB_CHECK(hipHostMalloc(&job->h_tot, sizeof(StepTotals)));
+    HIP_CHECK(hipMalloc(&job->d_rank, n * sizeof(RankRec)));
+    HIP_CHECK(hipMalloc(&job->d_dstoff, n * sizeof(uint64_t)));
+    HIP_CHECK(hipMalloc(&job->d_pos, n * sizeof(uint32_t)));
+    HIP_CHECK(hipMalloc(&job->d_outindex, n * 16));
+    HIP_CHECK(hipMalloc(&job->d_srcmap, n * sizeof(uint64_t)));
+    HIP_CHECK(hipMalloc(&job->d_outdata, total_data ? total_data : 16));
+    HIP_CHECK(hipMalloc(&job->d_err, 2 * sizeof(uint32_t)));
+    HIP_CHECK(hipMalloc(&job->d_pfx, n * sizeof(uint64_t)));
+    HIP_CHECK(hipMalloc(&job->d_tot, sizeof(StepTotals)));
+    HIP_CHECK(hipHostMalloc(&job->h_tot, sizeof(StepTotals)));
     uint32_t max_job_runs = 1;
     {
         for (size_t j = 0; j < n_jobs; j++)
             if (runs_per_job[j] > max_job_runs)
                 max_job_runs = runs_per_job[j];
     }
-    JOB_CHECK(hipMalloc(&job->d_cr,
+    HIP_CHECK(hipMalloc(&job->d_cr,
                         (max_job_runs > 1 ? (max_job_runs - 1) * n : 1) *
                             4));
     /* sized for the smallest copy-window variant (8 KiB) */
-    JOB_CHECK(hipMalloc(&job->d_winp0,
+    HIP_CHECK(hipMalloc(&job->d_winp0,
                         (total_data / 8192 + 2) * sizeof(uint32_t)));
 
-    size_t t1 = 0, t2 = 0;
-    rocprim::exclusive_scan(nullptr, t1,
-                            rocprim::make_transform_iterator(job->d_rank,
-                                                             RankRecSize{}),
-                            job->d_dstoff, (uint64_t)0, n,
-                            rocprim::plus<uint64_t>(), job->stream);
-    rocprim::exclusive_scan(nullptr, t2,
-                            rocprim::make_transform_iterator(job->d_rank,
-                                                             RankRecFlag{}),
-                            job->d_pos, (uint32_t)0, n,
-                            rocprim::plus<uint32_t>(), job->stream);
-    job->scantmp_bytes = t1 > t2 ? t1 : t2;
-    JOB_CHECK(hipMalloc(&job->d_scantmp, job->scantmp_bytes));
+    HIP_CHECK(survivor_scans(nullptr, job->scantmp_bytes, job->d_rank,
+                             job->d_dstoff, job->d_pos, n, job->stream));
+    HIP_CHECK(hipMalloc(&job->d_scantmp, job->scantmp_bytes));
 
     /* Upload: one slab; record per-run device pointers. */
-    JOB_CHECK(hipEventRecord(job->ev[0], job->stream));
+    HIP_CHECK(hipEventRecord(job->ev[0], job->stream));
     uint8_t* p = borrowed ? nullptr : job->d_input + 16;
     RunsDesc& D = job->desc;
     memset(&D, 0, sizeof D);
@@ -1658,14 +1734,14 @@ static int job_create_impl(const dbeel_run_view* runs, size_t n_runs,
         D.data[r] = borrowed ? runs[r].data : p;
         D.data_len[r] = runs[r].data_len;
         if (runs[r].data_len && !borrowed) {
-            JOB_CHECK(hipMemcpyAsync(p, runs[r].data, runs[r].data_len,
+            HIP_CHECK(hipMemcpyAsync(p, runs[r].data, runs[r].data_len,
                                      hipMemcpyHostToDevice, job->stream));
             p += runs[r].data_len;
         }
         D.index[r] = borrowed ? runs[r].index : p;
         D.count[r] = runs[r].index_len / 16;
         if (runs[r].index_len && !borrowed) {
-            JOB_CHECK(hipMemcpyAsync(p, runs[r].index, runs[r].index_len,
+            HIP_CHECK(hipMemcpyAsync(p, runs[r].index, runs[r].index_len,
                                      hipMemcpyHostToDevice, job->stream));
             p += runs[r].index_len;
         }
@@ -1674,52 +1750,24 @@ static int job_create_impl(const dbeel_run_view* runs, size_t n_runs,
     }
     /* merge-path pair table: one entry per unordered run pair with work */
     {
-        struct HostPair { uint32_t a, b; uint64_t chunk_base; };
-        size_t max_pairs = n_runs * (n_runs - 1) / 2 + 1;
-        HostPair* hp = (HostPair*)malloc(max_pairs * sizeof(HostPair));
-        if (!hp) {
-            dbeel_gpu_job_destroy(job);
-            return DBEEL_ERR_OOM;
-        }
+        /* 32 KiB on the stack: nothing to allocate, nothing to fail */
+        PairDesc hp[MAX_RUNS * (MAX_RUNS - 1) / 2];
         uint64_t cbase = 0;
         uint32_t np = 0;
         for (uint32_t a = 0; a < n_runs; a++)
             for (uint32_t b = a + 1; b < D.job_hi[a]; b++) {
                 uint64_t len = D.count[a] + D.count[b];
                 if (!len) continue;
-                hp[np].a = a;
-                hp[np].b = b;
-                hp[np].chunk_base = cbase;
+                hp[np++] = {a, b, cbase};
                 cbase += (len + CORANK_BLOCK_POS - 1) / CORANK_BLOCK_POS;
-                np++;
             }
         job->n_pairs = np;
         job->total_chunks = cbase;
-        {
-            hipError_t _e = hipMalloc(&job->d_corners,
-                                      (cbase ? cbase : 1) * 8);
-            if (_e != hipSuccess) {
-                set_err("corner table alloc failed: %s",
-                        hipGetErrorString(_e));
-                free(hp);
-                dbeel_gpu_job_destroy(job);
-                return DBEEL_ERR_OOM;
-            }
-        }
+        HIP_CHECK(hipMalloc(&job->d_corners, (cbase ? cbase : 1) * 8));
         if (np) {
-            hipError_t _e = hipMalloc(&job->d_pairs, np * sizeof(PairDesc));
-            if (_e == hipSuccess)
-                _e = hipMemcpy(job->d_pairs, hp, np * sizeof(PairDesc),
-                               hipMemcpyHostToDevice);
-            free(hp);
-            if (_e != hipSuccess) {
-                set_err("pair table upload failed: %s",
-                        hipGetErrorString(_e));
-                dbeel_gpu_job_destroy(job);
-                return DBEEL_ERR_HIP;
-            }
-        } else {
-            free(hp);
+            HIP_CHECK(hipMalloc(&job->d_pairs, np * sizeof(PairDesc)));
+            HIP_CHECK(hipMemcpy(job->d_pairs, hp, np * sizeof(PairDesc),
+                                hipMemcpyHostToDevice));
         }
     }
     {
@@ -1730,35 +1778,37 @@ static int job_create_impl(const dbeel_run_view* runs, size_t n_runs,
         }
         job->job_gbase.push_back(total);
     }
-    JOB_CHECK(hipEventRecord(job->ev[1], job->stream));
-    JOB_CHECK(hipStreamSynchronize(job->stream));
+    HIP_CHECK(hipEventRecord(job->ev[1], job->stream));
+    HIP_CHECK(hipStreamSynchronize(job->stream));
     float ms = 0;
-    JOB_CHECK(hipEventElapsedTime(&ms, job->ev[0], job->ev[1]));
+    HIP_CHECK(hipEventElapsedTime(&ms, job->ev[0], job->ev[1]));
     job->h2d_ms = borrowed ? 0.0 : ms;
 
     /* pick the aux tier from the max key_size (index slabs are resident
      * now); the tier is a traffic optimization only — every tier is
      * correct for every key length (blob fallback on deep ties) */
     if (total) {
-        JOB_CHECK(hipMemsetAsync(job->d_err, 0, 8, job->stream));
+        HIP_CHECK(hipMemsetAsync(job->d_err, 0, 8, job->stream));
         hipLaunchKernelGGL(k_maxks, dim3(pick_grid(total, 256)), dim3(256),
                            0, job->stream, job->desc, job->d_err + 1);
         uint32_t maxks = 0;
-        JOB_CHECK(hipMemcpyAsync(&maxks, job->d_err + 1, 4,
+        HIP_CHECK(hipMemcpyAsync(&maxks, job->d_err + 1, 4,
                                  hipMemcpyDeviceToHost, job->stream));
-        JOB_CHECK(hipStreamSynchronize(job->stream));
+        HIP_CHECK(hipStreamSynchronize(job->stream));
         uint32_t maxklen = maxks > 8 ? maxks - 8 : 0;
         job->aux_kind = maxklen <= 20 ? 0 : (maxklen <= 32 ? 1 : 2);
     } else {
         job->aux_kind = 0;
     }
-    uint64_t aux_sz = job->aux_kind == 0 ? 16 : (job->aux_kind == 1 ? 48
-                                                                    : 64);
-    JOB_CHECK(hipMalloc(&job->d_aux, n * aux_sz));
+    uint64_t aux_sz = 0;
+    with_aux_tier(job->aux_kind, [&](auto tier) {
+        aux_sz = sizeof(typename decltype(tier)::Rec);
+    });
+    HIP_CHECK(hipMalloc(&job->d_aux, n * aux_sz));
 
+    drop_job.dismiss();
     *out_job = job;
     return DBEEL_OK;
-#undef JOB_CHECK
 }
 
 extern "C" int dbeel_gpu_job_create(const dbeel_run_view* runs,
@@ -1929,6 +1979,18 @@ extern "C" int dbeel_gpu_unpin_host(const void* ptr) {
     return DBEEL_OK;
 }
 
+/* k_prepare over the global entries [g0, g1) in the job's aux tier. */
+static void launch_prepare(dbeel_gpu_job* job, uint64_t g0, uint64_t g1,
+                           hipStream_t s) {
+    with_aux_tier(job->aux_kind, [&](auto tier) {
+        using T = decltype(tier);
+        hipLaunchKernelGGL((k_prepare<T::KB, T::TS>),
+                           dim3(pick_grid(g1 - g0, 256)), dim3(256), 0, s,
+                           job->desc, g0, g1, job->d_pfx,
+                           (typename T::Rec*)job->d_aux, job->d_err);
+    });
+}
+
 extern "C" int dbeel_gpu_job_ingest(dbeel_gpu_job* job,
                                     const dbeel_run_view* runs,
                                     size_t n_runs,
@@ -1974,47 +2036,34 @@ extern "C" int dbeel_gpu_job_ingest(dbeel_gpu_job* job,
     std::vector<hipEvent_t> evs;
     hipEvent_t ev_cs0 = nullptr, ev_cs1 = nullptr, ev_ks0 = nullptr,
                ev_ks1 = nullptr;
+    ScopeGuard destroy_events([&] {
+        for (hipEvent_t e : evs) hipEventDestroy(e);
+        for (hipEvent_t e : {ev_cs0, ev_cs1, ev_ks0, ev_ks1})
+            if (e) hipEventDestroy(e);
+    });
     HIP_CHECK(hipEventCreate(&ev_cs0));
     HIP_CHECK(hipEventCreate(&ev_cs1));
     HIP_CHECK(hipEventCreate(&ev_ks0));
     HIP_CHECK(hipEventCreate(&ev_ks1));
     HIP_CHECK(hipMemsetAsync(job->d_err, 0, 8, ks));
 
-    auto cleanup = [&]() {
-        for (hipEvent_t e : evs) hipEventDestroy(e);
-        hipEventDestroy(ev_cs0);
-        hipEventDestroy(ev_cs1);
-        hipEventDestroy(ev_ks0);
-        hipEventDestroy(ev_ks1);
-    };
-#define ING_CHECK(call)                                                     \
-    do {                                                                    \
-        hipError_t _e = (call);                                             \
-        if (_e != hipSuccess) {                                             \
-            set_err("%s failed: %s", #call, hipGetErrorString(_e));         \
-            cleanup();                                                      \
-            return (_e == hipErrorOutOfMemory) ? DBEEL_ERR_OOM              \
-                                               : DBEEL_ERR_HIP;             \
-        }                                                                   \
-    } while (0)
-
-    ING_CHECK(hipEventRecord(ev_cs0, cs));
-    ING_CHECK(hipEventRecord(ev_ks0, ks));
+    HIP_CHECK(hipEventRecord(ev_cs0, cs));
+    HIP_CHECK(hipEventRecord(ev_ks0, ks));
     uint64_t total_chunks = 0;
 
     /* index slabs first (small; prepare reads them for every entry) */
     for (size_t r = 0; r < n_runs; r++) {
         if (!runs[r].index_len) continue;
-        ING_CHECK(hipMemcpyAsync(
+        HIP_CHECK(hipMemcpyAsync(
             const_cast<uint8_t*>(job->desc.index[r]), runs[r].index,
             runs[r].index_len, hipMemcpyHostToDevice, cs));
     }
     {
         hipEvent_t e;
-        ING_CHECK(hipEventCreate(&e));
+        HIP_CHECK(hipEventCreate(&e));
         evs.push_back(e);
-        ING_CHECK(hipEventRecord(e, cs));
-        ING_CHECK(hipStreamWaitEvent(ks, e, 0));
+        HIP_CHECK(hipEventRecord(e, cs));
+        HIP_CHECK(hipStreamWaitEvent(ks, e, 0));
     }
 
     /* stream each run's data in entry-aligned chunks; launch the ranged
@@ -2028,20 +2077,7 @@ extern "C" int dbeel_gpu_job_ingest(dbeel_gpu_job* job,
              * is normally launched per data chunk) */
             if (n) {
                 uint64_t g0 = job->desc.entry_base[r];
-                uint64_t g1 = g0 + n;
-                uint32_t grid = pick_grid(n, 256);
-                switch (job->aux_kind) {
-#define PREP_EMPTY(KB, TS)                                                  \
-    case (KB == 12 ? 0 : (KB == 24 ? 1 : 2)):                               \
-        hipLaunchKernelGGL((k_prepare<KB, TS>), dim3(grid), dim3(256), 0,   \
-                           ks, job->desc, g0, g1, job->d_pfx,               \
-                           (AuxT<KB, TS>*)job->d_aux, job->d_err);          \
-        break;
-                    PREP_EMPTY(12, false)
-                    PREP_EMPTY(24, true)
-                    PREP_EMPTY(40, true)
-#undef PREP_EMPTY
-                }
+                launch_prepare(job, g0, g0 + n, ks);
             }
             continue;
         }
@@ -2080,47 +2116,32 @@ extern "C" int dbeel_gpu_job_ingest(dbeel_gpu_job* job,
                     b1 = dlen;
                 }
             }
-            ING_CHECK(hipMemcpyAsync(
+            HIP_CHECK(hipMemcpyAsync(
                 const_cast<uint8_t*>(job->desc.data[r]) + b0,
                 runs[r].data + b0, b1 - b0, hipMemcpyHostToDevice, cs));
             hipEvent_t e;
-            ING_CHECK(hipEventCreate(&e));
+            HIP_CHECK(hipEventCreate(&e));
             evs.push_back(e);
-            ING_CHECK(hipEventRecord(e, cs));
-            ING_CHECK(hipStreamWaitEvent(ks, e, 0));
-            if (e1 > e0) {
-                uint64_t g0 = job->desc.entry_base[r] + e0;
-                uint64_t g1 = job->desc.entry_base[r] + e1;
-                uint32_t grid = pick_grid(g1 - g0, 256);
-                switch (job->aux_kind) {
-#define PREP_RANGE(KB, TS)                                                  \
-    case (KB == 12 ? 0 : (KB == 24 ? 1 : 2)):                               \
-        hipLaunchKernelGGL((k_prepare<KB, TS>), dim3(grid), dim3(256), 0,   \
-                           ks, job->desc, g0, g1, job->d_pfx,               \
-                           (AuxT<KB, TS>*)job->d_aux, job->d_err);          \
-        break;
-                    PREP_RANGE(12, false)
-                    PREP_RANGE(24, true)
-                    PREP_RANGE(40, true)
-#undef PREP_RANGE
-                }
-            }
+            HIP_CHECK(hipEventRecord(e, cs));
+            HIP_CHECK(hipStreamWaitEvent(ks, e, 0));
+            if (e1 > e0)
+                launch_prepare(job, job->desc.entry_base[r] + e0,
+                               job->desc.entry_base[r] + e1, ks);
             total_chunks++;
             e0 = e1;
             b0 = b1;
         }
     }
 
-    ING_CHECK(hipEventRecord(ev_cs1, cs));
-    ING_CHECK(hipEventRecord(ev_ks1, ks));
+    HIP_CHECK(hipEventRecord(ev_cs1, cs));
+    HIP_CHECK(hipEventRecord(ev_ks1, ks));
     uint32_t err = 0;
-    ING_CHECK(hipMemcpyAsync(&err, job->d_err, 4, hipMemcpyDeviceToHost,
+    HIP_CHECK(hipMemcpyAsync(&err, job->d_err, 4, hipMemcpyDeviceToHost,
                              ks));
-    ING_CHECK(hipStreamSynchronize(cs));
-    ING_CHECK(hipStreamSynchronize(ks));
-    ING_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(cs));
+    HIP_CHECK(hipStreamSynchronize(ks));
+    HIP_CHECK(hipGetLastError());
     if (err) {
-        cleanup();
         set_err("corrupt entry/index record in streamed ingest");
         return DBEEL_ERR_CORRUPT;
     }
@@ -2139,9 +2160,7 @@ extern "C" int dbeel_gpu_job_ingest(dbeel_gpu_job* job,
     }
     job->h2d_ms = 0.0; /* transfer accounted in ingest stats */
     job->prep_valid = 1;
-    cleanup();
     return DBEEL_OK;
-#undef ING_CHECK
 }
 
 static uint32_t pick_grid(uint64_t work_items, uint32_t block) {
@@ -2234,6 +2253,8 @@ extern "C" int dbeel_gpu_job_run(dbeel_gpu_job* job, int keep_tombstones,
     HIP_CHECK(hipMemsetAsync(job->d_err, 0, 2 * sizeof(uint32_t), s));
 
     HIP_CHECK(hipEventRecord(job->ev[0], s));
+    if (n && !skip_prep) launch_prepare(job, 0, n, s);
+    HIP_CHECK(hipEventRecord(job->ev[6], s));
     if (n) {
         uint32_t grid = pick_grid(n, 256);
         uint64_t cgrid = job->total_chunks;
@@ -2241,51 +2262,36 @@ extern "C" int dbeel_gpu_job_run(dbeel_gpu_job* job, int keep_tombstones,
         int corank_wide = 0; /* A/B: 512-thread corank blocks */
         if (const char* w = getenv("DBEEL_CORANK_BLOCK"))
             corank_wide = atoi(w) >= 512;
-        switch (job->aux_kind) {
-#define STAGE1(KB, TS)                                                      \
-    case (KB == 12 ? 0 : (KB == 24 ? 1 : 2)):                               \
-        if (!skip_prep)                                                     \
-            hipLaunchKernelGGL((k_prepare<KB, TS>), dim3(grid), dim3(256),  \
-                               0, s, job->desc, (uint64_t)0, n, job->d_pfx, \
-                               (AuxT<KB, TS>*)job->d_aux, job->d_err);      \
-        hipEventRecord(job->ev[6], s);                                      \
-        if (job->n_pairs) {                                                 \
-            hipLaunchKernelGGL((k_corners<KB, TS>),                         \
-                               dim3(pick_grid(job->total_chunks, 256)),     \
-                               dim3(256), 0, s, job->desc, job->d_pfx,      \
-                               (const AuxT<KB, TS>*)job->d_aux,             \
-                               (const PairDesc*)job->d_pairs, job->n_pairs, \
-                               job->total_chunks, job->d_corners);          \
-            if (corank_wide)                                                \
-                hipLaunchKernelGGL((k_corank<KB, TS, 512>),                 \
-                                   dim3((uint32_t)cgrid), dim3(512), 0, s,  \
-                                   job->desc, job->d_pfx,                   \
-                                   (const AuxT<KB, TS>*)job->d_aux,         \
-                                   (const PairDesc*)job->d_pairs,           \
-                                   job->n_pairs, job->total_chunks,         \
-                                   job->d_corners, job->d_cr);              \
-            else                                                            \
-                hipLaunchKernelGGL((k_corank<KB, TS, 256>),                 \
-                                   dim3((uint32_t)cgrid),                   \
-                                   dim3(CORANK_BLOCK), 0, s, job->desc,     \
-                                   job->d_pfx,                              \
-                                   (const AuxT<KB, TS>*)job->d_aux,         \
-                                   (const PairDesc*)job->d_pairs,           \
-                                   job->n_pairs, job->total_chunks,         \
-                                   job->d_corners, job->d_cr);              \
-        }                                                                   \
-        hipLaunchKernelGGL((k_rankreduce<KB, TS>), dim3(grid), dim3(256),   \
-                           0, s, job->desc, job->d_pfx,                     \
-                           (const AuxT<KB, TS>*)job->d_aux, job->d_cr,      \
-                           job->d_rank, keep_tombstones, job->d_err);       \
-        break;
-            STAGE1(12, false)
-            STAGE1(24, true)
-            STAGE1(40, true)
-#undef STAGE1
-        }
-    } else {
-        HIP_CHECK(hipEventRecord(job->ev[6], s));
+        with_aux_tier(job->aux_kind, [&](auto tier) {
+            using T = decltype(tier);
+            constexpr int KB = T::KB;
+            constexpr bool TS = T::TS;
+            const typename T::Rec* aux = (const typename T::Rec*)job->d_aux;
+            const PairDesc* pairs = (const PairDesc*)job->d_pairs;
+            if (job->n_pairs) {
+                hipLaunchKernelGGL((k_corners<KB, TS>),
+                                   dim3(pick_grid(job->total_chunks, 256)),
+                                   dim3(256), 0, s, job->desc, job->d_pfx,
+                                   aux, pairs, job->n_pairs,
+                                   job->total_chunks, job->d_corners);
+                if (corank_wide)
+                    hipLaunchKernelGGL((k_corank<KB, TS, 512>),
+                                       dim3((uint32_t)cgrid), dim3(512), 0, s,
+                                       job->desc, job->d_pfx, aux, pairs,
+                                       job->n_pairs, job->total_chunks,
+                                       job->d_corners, job->d_cr);
+                else
+                    hipLaunchKernelGGL((k_corank<KB, TS, 256>),
+                                       dim3((uint32_t)cgrid),
+                                       dim3(CORANK_BLOCK), 0, s, job->desc,
+                                       job->d_pfx, aux, pairs, job->n_pairs,
+                                       job->total_chunks, job->d_corners,
+                                       job->d_cr);
+            }
+            hipLaunchKernelGGL((k_rankreduce<KB, TS>), dim3(grid), dim3(256),
+                               0, s, job->desc, job->d_pfx, aux, job->d_cr,
+                               job->d_rank, keep_tombstones, job->d_err);
+        });
     }
     HIP_CHECK(hipEventRecord(job->ev[1], s));
     bool packed = n < (1ull << 26) &&
@@ -2295,27 +2301,16 @@ extern "C" int dbeel_gpu_job_run(dbeel_gpu_job* job, int keep_tombstones,
     }
     if (n) {
         size_t tmp = job->scantmp_bytes;
-        if (packed) {
-            (void)rocprim::exclusive_scan(
+        if (packed)
+            HIP_CHECK(rocprim::exclusive_scan(
                 job->d_scantmp, tmp,
                 rocprim::make_transform_iterator(job->d_rank,
                                                  RankRecPacked{}),
                 job->d_dstoff, (uint64_t)0, n, rocprim::plus<uint64_t>(),
-                s);
-        } else {
-            (void)rocprim::exclusive_scan(
-                job->d_scantmp, tmp,
-                rocprim::make_transform_iterator(job->d_rank,
-                                                 RankRecSize{}),
-                job->d_dstoff, (uint64_t)0, n, rocprim::plus<uint64_t>(),
-                s);
-            tmp = job->scantmp_bytes;
-            (void)rocprim::exclusive_scan(
-                job->d_scantmp, tmp,
-                rocprim::make_transform_iterator(job->d_rank,
-                                                 RankRecFlag{}),
-                job->d_pos, (uint32_t)0, n, rocprim::plus<uint32_t>(), s);
-        }
+                s));
+        else
+            HIP_CHECK(survivor_scans(job->d_scantmp, tmp, job->d_rank,
+                                     job->d_dstoff, job->d_pos, n, s));
     }
     HIP_CHECK(hipEventRecord(job->ev[2], s));
     if (n) {
@@ -2546,20 +2541,7 @@ __global__ void k_lookup(RunsDesc R, const uint8_t* keys,
         uint64_t best_off = 0, best_vlen = 0;
         /* newest-index-first, first match wins (lsm_tree.rs:692-696) */
         for (int r = R.n_runs - 1; r >= 0; r--) {
-            uint64_t lo = 0, hi = R.count[r];
-            while (lo < hi) {
-                uint64_t mid = (lo + hi) >> 1;
-                EView m;
-                if (!load_entry(R, r, mid, m)) {
-                    hi = mid; /* corrupt input; search degrades safely */
-                    continue;
-                }
-                int c = cmp_keys(m.key, m.klen, key, klen);
-                if (c < 0)
-                    lo = mid + 1;
-                else
-                    hi = mid;
-            }
+            uint64_t lo = blob_lower_bound(R, r, 0, R.count[r], key, klen);
             if (lo >= R.count[r]) continue;
             EView m;
             if (!load_entry(R, r, lo, m)) continue;
@@ -2588,17 +2570,8 @@ extern "C" int dbeel_gpu_lookup(const dbeel_run_view* runs, size_t n_runs,
     }
     int rc = validate_runs(runs, n_runs);
     if (rc) return rc;
-    if (device < 0) {
-        set_err("device must be >= 0 (no CPU fallback)");
-        return DBEEL_ERR_INVALID_ARG;
-    }
-    int ndev = 0;
-    hipError_t de = hipGetDeviceCount(&ndev);
-    if (de != hipSuccess || device >= ndev) {
-        set_err("no usable HIP device %d", device);
-        return DBEEL_ERR_NO_GPU;
-    }
-    HIP_CHECK(hipSetDevice(device));
+    rc = select_device(device);
+    if (rc) return rc;
     if (n_keys == 0) return DBEEL_OK;
 
     dbeel_gpu_job* job = nullptr;
@@ -2692,33 +2665,23 @@ __global__ void k_reader_prepare(RunsDesc R, uint64_t* pfx, uint32_t* err) {
     uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
          g < R.total; g += stride) {
-        int r = 0;
-        while (r + 1 < R.n_runs && g >= R.entry_base[r + 1]) r++;
+        int r = run_of(R, g);
         uint64_t i = g - R.entry_base[r];
         EView e;
-        /* offset checked on its own first: off + full_size must not wrap */
-        if (ld_u64(R.index[r] + i * 16) > R.data_len[r] ||
-            !load_entry(R, r, i, e)) {
+        if (!load_entry(R, r, i, e)) {
             atomicOr(err, DERR_CORRUPT);
             pfx[g] = 0;
             continue;
         }
         pfx[g] = key_prefix(e.key, e.klen);
-        /* bincode field cross-check */
-        if (ld_u64(e.raw) != e.klen ||
-            ld_u64(e.raw + 8 + e.klen) != (uint64_t)e.full_size - 32 - e.klen)
-            atomicOr(err, DERR_CORRUPT);
-        if (i + 1 < R.count[r]) {
-            uint64_t noff = ld_u64(R.index[r] + (i + 1) * 16);
-            if (e.off + e.full_size > noff) atomicOr(err, DERR_CORRUPT);
-            /* the search depends on strictly ascending keys
-             * (flush invariant, lsm_tree.rs:925-946); an invalid
-             * successor is flagged by its own thread */
-            EView nx;
-            if (noff <= R.data_len[r] && load_entry(R, r, i + 1, nx) &&
-                cmp_keys(e.key, e.klen, nx.key, nx.klen) >= 0)
-                atomicOr(err, DERR_UNSORTED);
-        }
+        if (!entry_consistent(R, r, i, e)) atomicOr(err, DERR_CORRUPT);
+        /* the search depends on strictly ascending keys (flush invariant,
+         * lsm_tree.rs:925-946); an invalid successor is flagged by its own
+         * thread */
+        EView nx;
+        if (i + 1 < R.count[r] && load_entry(R, r, i + 1, nx) &&
+            cmp_keys(e.key, e.klen, nx.key, nx.klen) >= 0)
+            atomicOr(err, DERR_UNSORTED);
     }
 }
 
@@ -2770,33 +2733,20 @@ __global__ __launch_bounds__(READER_BLOCK) void k_reader_search(
             c[RS_SEARCHES]++;
             const uint64_t* P = pfx.p[r];
             const uint64_t n = R.count[r];
-            uint64_t lo = 0, hi = n;
-            while (lo < hi) {
-                uint64_t mid = (lo + hi) >> 1;
-                if (P[mid] < qp)
-                    lo = mid + 1;
-                else
-                    hi = mid;
-            }
+            uint64_t lo = pfx_lower_bound(P, n, qp);
             if (lo >= n || P[lo] != qp) continue;
             /* [lo, end) = entries sharing the query's prefix. Usually
              * one entry; otherwise its end is found by a second
              * bisection, never a walk */
             uint64_t end = lo + 1;
-            if (end < n && P[end] == qp) {
-                uint64_t a = end + 1, b = n;
-                while (a < b) {
-                    uint64_t mid = (a + b) >> 1;
-                    if (P[mid] <= qp)
-                        a = mid + 1;
-                    else
-                        b = mid;
-                }
-                end = a;
-            }
+            if (end < n && P[end] == qp)
+                end = pfx_upper_bound(P, end + 1, n, qp);
             /* equal prefixes are not equal keys (zero padding, length,
              * bytes past 8): the full compare on the blob decides. Keys
-             * are unique inside a run, so a zero compare is the match */
+             * are unique inside a run, so a zero compare is the match and
+             * ends the bisection with the entry in hand — which is why
+             * this is not blob_lower_bound, whose answer would have to be
+             * loaded and compared once more */
             bool found = false;
             EView m;
             while (lo < end) {
@@ -3157,10 +3107,8 @@ extern "C" int dbeel_gpu_reader_open(const dbeel_run_view* runs,
     *out_reader = nullptr;
     int rc = validate_runs(runs, n_runs);
     if (rc) return rc;
-    if (device < 0) {
-        set_err("device must be >= 0 (no CPU fallback)");
-        return DBEEL_ERR_INVALID_ARG;
-    }
+    rc = check_device_arg(device);
+    if (rc) return rc;
     ReaderBloom hb[MAX_RUNS];
     memset(hb, 0, sizeof hb);
     for (size_t r = 0; r < n_runs; r++) {
@@ -3169,60 +3117,43 @@ extern "C" int dbeel_gpu_reader_open(const dbeel_run_view* runs,
         if (rc) return rc;
     }
 
-    int ndev = 0;
-    hipError_t de = hipGetDeviceCount(&ndev);
-    if (de != hipSuccess || device >= ndev) {
-        set_err("no usable HIP device %d (count=%d, %s)", device, ndev,
-                hipGetErrorString(de));
-        return DBEEL_ERR_NO_GPU;
-    }
-    HIP_CHECK(hipSetDevice(device));
+    rc = select_device(device);
+    if (rc) return rc;
 
     dbeel_gpu_reader* rd = new (std::nothrow) dbeel_gpu_reader();
     if (!rd) return DBEEL_ERR_OOM;
+    ScopeGuard close_rd([&] { dbeel_gpu_reader_close(rd); });
     rd->device = device;
-
-#define RD_CHECK(call)                                                      \
-    do {                                                                    \
-        hipError_t _e = (call);                                             \
-        if (_e != hipSuccess) {                                             \
-            set_err("%s failed: %s", #call, hipGetErrorString(_e));         \
-            dbeel_gpu_reader_close(rd);                                     \
-            return (_e == hipErrorOutOfMemory) ? DBEEL_ERR_OOM              \
-                                               : DBEEL_ERR_HIP;             \
-        }                                                                   \
-    } while (0)
 
     uint32_t* d_err = nullptr;
     uint32_t err = 0;
 
-    RD_CHECK(hipStreamCreate(&rd->stream));
-    for (int i = 0; i < 7; i++) RD_CHECK(hipEventCreate(&rd->ev[i]));
-    RD_CHECK(hipMalloc(&rd->d_blooms, MAX_RUNS * sizeof(ReaderBloom)));
-    RD_CHECK(hipMalloc(&rd->d_stats, (RS_N + 1) * sizeof(uint64_t)));
+    HIP_CHECK(hipStreamCreate(&rd->stream));
+    for (int i = 0; i < 7; i++) HIP_CHECK(hipEventCreate(&rd->ev[i]));
+    HIP_CHECK(hipMalloc(&rd->d_blooms, MAX_RUNS * sizeof(ReaderBloom)));
+    HIP_CHECK(hipMalloc(&rd->d_stats, (RS_N + 1) * sizeof(uint64_t)));
     d_err = (uint32_t*)(rd->d_stats + RS_N);
-    RD_CHECK(hipMemsetAsync(d_err, 0, sizeof(uint64_t), rd->stream));
+    HIP_CHECK(hipMemsetAsync(d_err, 0, sizeof(uint64_t), rd->stream));
     rd->tables.reserve(MAX_RUNS);
     for (size_t r = 0; r < n_runs; r++) {
         const bool filtered = blooms && blooms[r].bytes;
         ReaderTable t;
-        RD_CHECK(reader_upload_table(rd, runs[r],
-                                     filtered ? &blooms[r] : nullptr,
-                                     filtered ? &hb[r] : nullptr, d_err, t));
+        HIP_CHECK(reader_upload_table(rd, runs[r],
+                                      filtered ? &blooms[r] : nullptr,
+                                      filtered ? &hb[r] : nullptr, d_err, t));
         rd->tables.push_back(t);
     }
-    RD_CHECK(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost,
-                            rd->stream));
+    HIP_CHECK(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost,
+                             rd->stream));
     /* the caller's buffers are read by the async copies above */
-    RD_CHECK(hipStreamSynchronize(rd->stream));
-    RD_CHECK(hipGetLastError());
-    RD_CHECK(reader_link(rd));
-#undef RD_CHECK
+    HIP_CHECK(hipStreamSynchronize(rd->stream));
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(reader_link(rd));
     if (err) {
         set_err_prepare(err);
-        dbeel_gpu_reader_close(rd);
         return DBEEL_ERR_CORRUPT;
     }
+    close_rd.dismiss();
     *out_reader = rd;
     return DBEEL_OK;
 }
@@ -3582,99 +3513,86 @@ extern "C" int dbeel_gpu_reader_get(dbeel_gpu_reader* rd,
     /* d_batch layout: key offsets (n+1) | value offsets (n+1) | hits (n+1,
      * the last one zeroed so the scan's final element is the total) */
     const uint64_t off_bytes = (n + 1) * sizeof(uint64_t);
-    uint64_t* d_koff = nullptr;
-    uint64_t* d_voff = nullptr;
-    dbeel_lookup_hit* d_hits = nullptr;
     size_t tmp_bytes = 0;
     uint64_t total = 0;
     unsigned long long hstats[RS_N] = {};
     float ms[6] = {};
-    int rc = DBEEL_OK;
     hipStream_t s = rd->stream;
+    /* on failure nothing of this batch may still be in flight into freed
+     * memory */
+    ScopeGuard fail([&] {
+        (void)hipStreamSynchronize(s);
+        dbeel_gpu_get_result_free(out);
+    });
 
-#define GET_CHECK(call)                                                     \
-    do {                                                                    \
-        hipError_t _e = (call);                                             \
-        if (_e != hipSuccess) {                                             \
-            set_err("%s failed: %s", #call, hipGetErrorString(_e));         \
-            rc = (_e == hipErrorOutOfMemory) ? DBEEL_ERR_OOM                \
-                                             : DBEEL_ERR_HIP;               \
-            goto done;                                                      \
-        }                                                                   \
-    } while (0)
-
-    GET_CHECK(hipSetDevice(rd->device));
-    GET_CHECK(reader_reserve((void**)&rd->d_keys, &rd->keys_cap,
+    HIP_CHECK(hipSetDevice(rd->device));
+    HIP_CHECK(reader_reserve((void**)&rd->d_keys, &rd->keys_cap,
                              kbytes ? kbytes : 1));
-    GET_CHECK(reader_reserve((void**)&rd->d_batch, &rd->batch_cap,
+    HIP_CHECK(reader_reserve((void**)&rd->d_batch, &rd->batch_cap,
                              2 * off_bytes +
                                  (n + 1) * sizeof(dbeel_lookup_hit)));
-    d_koff = (uint64_t*)rd->d_batch;
-    d_voff = d_koff + (n + 1);
-    d_hits = (dbeel_lookup_hit*)(d_voff + (n + 1));
-    (void)rocprim::exclusive_scan(
+    uint64_t* d_koff = (uint64_t*)rd->d_batch;
+    uint64_t* d_voff = d_koff + (n + 1);
+    dbeel_lookup_hit* d_hits = (dbeel_lookup_hit*)(d_voff + (n + 1));
+    HIP_CHECK(rocprim::exclusive_scan(
         nullptr, tmp_bytes,
         rocprim::make_transform_iterator(d_hits, HitValueLen{}), d_voff,
-        (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), s);
-    GET_CHECK(reader_reserve(&rd->d_scantmp, &rd->scantmp_cap,
+        (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), s));
+    HIP_CHECK(reader_reserve(&rd->d_scantmp, &rd->scantmp_cap,
                              tmp_bytes ? tmp_bytes : 1));
 
-    GET_CHECK(hipEventRecord(rd->ev[0], s));
+    HIP_CHECK(hipEventRecord(rd->ev[0], s));
     if (kbytes)
-        GET_CHECK(hipMemcpyAsync(rd->d_keys, keys, kbytes,
+        HIP_CHECK(hipMemcpyAsync(rd->d_keys, keys, kbytes,
                                  hipMemcpyHostToDevice, s));
-    GET_CHECK(hipMemcpyAsync(d_koff, key_offsets, off_bytes,
+    HIP_CHECK(hipMemcpyAsync(d_koff, key_offsets, off_bytes,
                              hipMemcpyHostToDevice, s));
-    GET_CHECK(hipMemsetAsync(rd->d_stats, 0, RS_N * sizeof(uint64_t), s));
-    GET_CHECK(hipMemsetAsync(d_hits + n, 0, sizeof(dbeel_lookup_hit), s));
-    GET_CHECK(hipEventRecord(rd->ev[1], s));
+    HIP_CHECK(hipMemsetAsync(rd->d_stats, 0, RS_N * sizeof(uint64_t), s));
+    HIP_CHECK(hipMemsetAsync(d_hits + n, 0, sizeof(dbeel_lookup_hit), s));
+    HIP_CHECK(hipEventRecord(rd->ev[1], s));
     hipLaunchKernelGGL(k_reader_search, dim3(pick_grid(n, READER_BLOCK)),
                        dim3(READER_BLOCK), 0, s, rd->desc, rd->pfx,
                        rd->d_blooms, rd->d_keys, d_koff, n, d_hits,
                        rd->d_stats);
-    GET_CHECK(hipEventRecord(rd->ev[2], s));
-    {
-        hipError_t se = rocprim::exclusive_scan(
-            rd->d_scantmp, tmp_bytes,
-            rocprim::make_transform_iterator(d_hits, HitValueLen{}), d_voff,
-            (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), s);
-        GET_CHECK(se);
-    }
-    GET_CHECK(hipEventRecord(rd->ev[3], s));
-    GET_CHECK(hipMemcpyAsync(&total, d_voff + n, 8, hipMemcpyDeviceToHost,
+    HIP_CHECK(hipEventRecord(rd->ev[2], s));
+    HIP_CHECK(rocprim::exclusive_scan(
+        rd->d_scantmp, tmp_bytes,
+        rocprim::make_transform_iterator(d_hits, HitValueLen{}), d_voff,
+        (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), s));
+    HIP_CHECK(hipEventRecord(rd->ev[3], s));
+    HIP_CHECK(hipMemcpyAsync(&total, d_voff + n, 8, hipMemcpyDeviceToHost,
                              s));
-    GET_CHECK(hipStreamSynchronize(s));
-    GET_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipGetLastError());
     out->values = (uint8_t*)malloc(total ? total : 1);
     if (!out->values) {
         set_err("host malloc of %llu value bytes failed",
                 (unsigned long long)total);
-        rc = DBEEL_ERR_OOM;
-        goto done;
+        return DBEEL_ERR_OOM;
     }
     if (total)
-        GET_CHECK(reader_reserve((void**)&rd->d_values, &rd->values_cap,
+        HIP_CHECK(reader_reserve((void**)&rd->d_values, &rd->values_cap,
                                  total));
-    GET_CHECK(hipEventRecord(rd->ev[4], s));
+    HIP_CHECK(hipEventRecord(rd->ev[4], s));
     if (total)
         hipLaunchKernelGGL(k_reader_gather, dim3(pick_grid(n * 64, 256)),
                            dim3(256), 0, s, rd->desc, d_hits, d_voff, n,
                            rd->d_values);
-    GET_CHECK(hipEventRecord(rd->ev[5], s));
-    GET_CHECK(hipMemcpyAsync(out->hits, d_hits, n * sizeof *out->hits,
+    HIP_CHECK(hipEventRecord(rd->ev[5], s));
+    HIP_CHECK(hipMemcpyAsync(out->hits, d_hits, n * sizeof *out->hits,
                              hipMemcpyDeviceToHost, s));
-    GET_CHECK(hipMemcpyAsync(out->value_offsets, d_voff, off_bytes,
+    HIP_CHECK(hipMemcpyAsync(out->value_offsets, d_voff, off_bytes,
                              hipMemcpyDeviceToHost, s));
     if (total)
-        GET_CHECK(hipMemcpyAsync(out->values, rd->d_values, total,
+        HIP_CHECK(hipMemcpyAsync(out->values, rd->d_values, total,
                                  hipMemcpyDeviceToHost, s));
-    GET_CHECK(hipMemcpyAsync(hstats, rd->d_stats, sizeof hstats,
+    HIP_CHECK(hipMemcpyAsync(hstats, rd->d_stats, sizeof hstats,
                              hipMemcpyDeviceToHost, s));
-    GET_CHECK(hipEventRecord(rd->ev[6], s));
-    GET_CHECK(hipStreamSynchronize(s));
-    GET_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(rd->ev[6], s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipGetLastError());
     for (int i = 0; i < 6; i++)
-        GET_CHECK(hipEventElapsedTime(&ms[i], rd->ev[i], rd->ev[i + 1]));
+        HIP_CHECK(hipEventElapsedTime(&ms[i], rd->ev[i], rd->ev[i + 1]));
     out->values_len = total;
     out->n_keys = n;
     if (stats) {
@@ -3691,14 +3609,8 @@ extern "C" int dbeel_gpu_reader_get(dbeel_gpu_reader* rd,
         stats->hits = hstats[RS_HITS];
         stats->tombstones = hstats[RS_TOMBS];
     }
-done:
-    if (rc != DBEEL_OK) {
-        /* nothing of this batch may still be in flight into freed memory */
-        (void)hipStreamSynchronize(s);
-        dbeel_gpu_get_result_free(out);
-    }
-    return rc;
-#undef GET_CHECK
+    fail.dismiss();
+    return DBEEL_OK;
 }
 
 /* ------------------------------------------------------------------ */
@@ -3780,8 +3692,7 @@ __global__ void k_scanflag(RunsDesc R, const uint8_t* kbounds,
     uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
          g < R.total; g += stride) {
-        int r = 0;
-        while (r + 1 < R.n_runs && g >= R.entry_base[r + 1]) r++;
+        int r = run_of(R, g);
         uint64_t i = g - R.entry_base[r];
         EView e;
         if (!load_entry(R, r, i, e)) {
@@ -3862,15 +3773,10 @@ extern "C" int dbeel_gpu_scan(const dbeel_run_view* runs, size_t n_runs,
                            d_ranges + n_ranges, (uint32_t)n_ranges,
                            job->d_rank, job->d_err);
         size_t tmp = job->scantmp_bytes;
-        (void)rocprim::exclusive_scan(
-            job->d_scantmp, tmp,
-            rocprim::make_transform_iterator(job->d_rank, RankRecSize{}),
-            job->d_dstoff, (uint64_t)0, n, rocprim::plus<uint64_t>(), s);
-        tmp = job->scantmp_bytes;
-        (void)rocprim::exclusive_scan(
-            job->d_scantmp, tmp,
-            rocprim::make_transform_iterator(job->d_rank, RankRecFlag{}),
-            job->d_pos, (uint32_t)0, n, rocprim::plus<uint32_t>(), s);
+        e = survivor_scans(job->d_scantmp, tmp, job->d_rank, job->d_dstoff,
+                           job->d_pos, n, s);
+    }
+    if (e == hipSuccess && n) {
         hipLaunchKernelGGL(k_emit, dim3(pick_grid(n, 256)), dim3(256), 0,
                            s, job->desc, job->d_rank, job->d_dstoff,
                            job->d_pos, n, job->d_outindex, job->d_srcmap,
@@ -3965,37 +3871,11 @@ __global__ void k_reader_scan_bounds(RunsDesc R, ReaderPfx pfx,
     const uint64_t klen = is_end ? end_len : start_len;
     const uint64_t qp = key_prefix(key, klen);
     const uint64_t* P = pfx.p[r];
-    uint64_t lo = 0, hi = n; /* first prefix >= qp */
-    while (lo < hi) {
-        uint64_t mid = (lo + hi) >> 1;
-        if (P[mid] < qp)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    uint64_t a = lo, end = n; /* first prefix > qp */
-    while (a < end) {
-        uint64_t mid = (a + end) >> 1;
-        if (P[mid] <= qp)
-            a = mid + 1;
-        else
-            end = mid;
-    }
+    const uint64_t lo = pfx_lower_bound(P, n, qp);
+    const uint64_t end = pfx_upper_bound(P, lo, n, qp);
     /* [lo, end) share the bound's prefix and are in key order: the first
      * one >= the bound is the answer (end when there is none) */
-    while (lo < end) {
-        uint64_t mid = (lo + end) >> 1;
-        EView m;
-        if (!load_entry(R, r, mid, m)) { /* validated at open */
-            end = mid;
-            continue;
-        }
-        if (cmp_keys(m.key, m.klen, key, klen) < 0)
-            lo = mid + 1;
-        else
-            end = mid;
-    }
-    bounds[t] = lo;
+    bounds[t] = blob_lower_bound(R, r, lo, end, key, klen);
 }
 
 __global__ void k_reader_scan_flag(RunsDesc R, ScanWin W, uint64_t c0,
@@ -4286,73 +4166,42 @@ extern "C" int dbeel_gpu_reader_scan_next(dbeel_gpu_reader_scan* sc,
     const uint64_t scratch = o_rido + scan_align16(max_entries * 4);
 
     hipStream_t s = rd->stream;
-    int rc = DBEEL_OK;
-    float ms[5] = {};
-    size_t t1 = 0, t2 = 0;
-    RankRec* d_rrec = nullptr;
-    uint64_t* d_dst = nullptr;
-    uint32_t* d_pos = nullptr;
-    uint32_t* d_rid = nullptr;
-    uint8_t* d_oidx = nullptr;
-    uint64_t* d_smap = nullptr;
-    uint32_t* d_rido = nullptr;
-    uint64_t taken = 0, bytes = 0, next = 0;
+    /* on failure nothing of this page may still be in flight into the
+     * caller's buffers or the shared scratch */
+    ScopeGuard sync_on_fail([&] { (void)hipStreamSynchronize(s); });
 
-#define SCAN_CHECK(call)                                                    \
-    do {                                                                    \
-        hipError_t _e = (call);                                             \
-        if (_e != hipSuccess) {                                             \
-            set_err("%s failed: %s", #call, hipGetErrorString(_e));         \
-            rc = (_e == hipErrorOutOfMemory) ? DBEEL_ERR_OOM                \
-                                             : DBEEL_ERR_HIP;               \
-            goto done;                                                      \
-        }                                                                   \
-    } while (0)
-
-    SCAN_CHECK(hipSetDevice(rd->device));
-    SCAN_CHECK(reader_reserve((void**)&rd->d_scan, &rd->scan_cap, scratch));
-    SCAN_CHECK(reader_reserve((void**)&rd->d_page, &rd->page_cap,
-                              scan_align16(cap ? cap : 16)));
+    HIP_CHECK(hipSetDevice(rd->device));
+    HIP_CHECK(reader_reserve((void**)&rd->d_scan, &rd->scan_cap, scratch));
+    HIP_CHECK(reader_reserve((void**)&rd->d_page, &rd->page_cap,
+                             scan_align16(cap ? cap : 16)));
     /* sized for the smallest copy-window variant (8 KiB) */
-    SCAN_CHECK(reader_reserve((void**)&rd->d_scanwin, &rd->scanwin_cap,
-                              (cap / 8192 + 2) * sizeof(uint32_t)));
-    d_rrec = (RankRec*)(rd->d_scan + o_rrec);
-    d_dst = (uint64_t*)(rd->d_scan + o_dst);
-    d_pos = (uint32_t*)(rd->d_scan + o_pos);
-    d_rid = (uint32_t*)(rd->d_scan + o_rid);
-    d_oidx = rd->d_scan + o_oidx;
-    d_smap = (uint64_t*)(rd->d_scan + o_smap);
-    d_rido = (uint32_t*)(rd->d_scan + o_rido);
-    (void)rocprim::exclusive_scan(
-        nullptr, t1, rocprim::make_transform_iterator(d_rrec, RankRecSize{}),
-        d_dst, (uint64_t)0, m, rocprim::plus<uint64_t>(), s);
-    (void)rocprim::exclusive_scan(
-        nullptr, t2, rocprim::make_transform_iterator(d_rrec, RankRecFlag{}),
-        d_pos, (uint32_t)0, m, rocprim::plus<uint32_t>(), s);
-    if (t2 > t1) t1 = t2;
-    SCAN_CHECK(reader_reserve(&rd->d_scantmp, &rd->scantmp_cap, t1 ? t1 : 1));
+    HIP_CHECK(reader_reserve((void**)&rd->d_scanwin, &rd->scanwin_cap,
+                             (cap / 8192 + 2) * sizeof(uint32_t)));
+    RankRec* d_rrec = (RankRec*)(rd->d_scan + o_rrec);
+    uint64_t* d_dst = (uint64_t*)(rd->d_scan + o_dst);
+    uint32_t* d_pos = (uint32_t*)(rd->d_scan + o_pos);
+    uint32_t* d_rid = (uint32_t*)(rd->d_scan + o_rid);
+    uint8_t* d_oidx = rd->d_scan + o_oidx;
+    uint64_t* d_smap = (uint64_t*)(rd->d_scan + o_smap);
+    uint32_t* d_rido = (uint32_t*)(rd->d_scan + o_rido);
+    size_t tmp_bytes = 0;
+    HIP_CHECK(survivor_scans(nullptr, tmp_bytes, d_rrec, d_dst, d_pos, m, s));
+    HIP_CHECK(reader_reserve(&rd->d_scantmp, &rd->scantmp_cap,
+                             tmp_bytes ? tmp_bytes : 1));
 
-    SCAN_CHECK(hipEventRecord(rd->ev[0], s));
+    HIP_CHECK(hipEventRecord(rd->ev[0], s));
     hipLaunchKernelGGL(k_reader_scan_flag, dim3(pick_grid(m, 256)), dim3(256),
                        0, s, D, sc->win, sc->cursor, m, sc->d_ranges,
                        sc->d_ranges + sc->n_ranges, sc->n_ranges, d_rrec,
                        d_rid);
-    SCAN_CHECK(hipEventRecord(rd->ev[1], s));
-    t2 = t1;
-    SCAN_CHECK(rocprim::exclusive_scan(
-        rd->d_scantmp, t2,
-        rocprim::make_transform_iterator(d_rrec, RankRecSize{}), d_dst,
-        (uint64_t)0, m, rocprim::plus<uint64_t>(), s));
-    t2 = t1;
-    SCAN_CHECK(rocprim::exclusive_scan(
-        rd->d_scantmp, t2,
-        rocprim::make_transform_iterator(d_rrec, RankRecFlag{}), d_pos,
-        (uint32_t)0, m, rocprim::plus<uint32_t>(), s));
+    HIP_CHECK(hipEventRecord(rd->ev[1], s));
+    HIP_CHECK(survivor_scans(rd->d_scantmp, tmp_bytes, d_rrec, d_dst, d_pos,
+                             m, s));
     hipLaunchKernelGGL(k_reader_scan_emit, dim3(pick_grid(m, 256)), dim3(256),
                        0, s, D, d_rrec, d_rid, d_dst, d_pos, m,
                        (uint64_t)data_cap, max_entries, d_oidx, d_smap,
                        d_rido, rd->d_scantot);
-    SCAN_CHECK(hipEventRecord(rd->ev[2], s));
+    HIP_CHECK(hipEventRecord(rd->ev[2], s));
     {
         /* the copy's grid comes from an upper bound on the page's bytes,
          * its geometry from the tables' average entry size */
@@ -4360,19 +4209,18 @@ extern "C" int dbeel_gpu_reader_scan_next(dbeel_gpu_reader_scan* sc,
         launch_copy(s, d_oidx, d_smap, rd->d_scanwin, &rd->d_scantot->st,
                     avg ? (cap + avg - 1) / avg : 0, cap, rd->d_page);
     }
-    SCAN_CHECK(hipEventRecord(rd->ev[3], s));
-    SCAN_CHECK(hipMemcpyAsync(rd->h_scantot, rd->d_scantot,
-                              sizeof(ScanPageTotals), hipMemcpyDeviceToHost,
-                              s));
-    SCAN_CHECK(hipStreamSynchronize(s));
-    SCAN_CHECK(hipGetLastError());
-    taken = rd->h_scantot->st.n_surv;
-    bytes = rd->h_scantot->st.total_out;
-    next = rd->h_scantot->next;
+    HIP_CHECK(hipEventRecord(rd->ev[3], s));
+    HIP_CHECK(hipMemcpyAsync(rd->h_scantot, rd->d_scantot,
+                             sizeof(ScanPageTotals), hipMemcpyDeviceToHost,
+                             s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipGetLastError());
+    const uint64_t taken = rd->h_scantot->st.n_surv;
+    const uint64_t bytes = rd->h_scantot->st.total_out;
+    const uint64_t next = rd->h_scantot->next;
     if (taken > max_entries || bytes > cap || next > m) {
         set_err("reader_scan_next: inconsistent page totals");
-        rc = DBEEL_ERR_HIP;
-        goto done;
+        return DBEEL_ERR_HIP;
     }
     if (taken == 0 && next < m) {
         /* the first survivor alone exceeds data_cap (index_cap holds at
@@ -4381,24 +4229,24 @@ extern "C" int dbeel_gpu_reader_scan_next(dbeel_gpu_reader_scan* sc,
         set_err("reader_scan_next: entry of %llu bytes does not fit the "
                 "%zu-byte page buffer",
                 (unsigned long long)page->needed, data_cap);
-        rc = DBEEL_ERR_ITEM_TOO_LARGE;
-        goto done;
+        return DBEEL_ERR_ITEM_TOO_LARGE;
     }
-    SCAN_CHECK(hipEventRecord(rd->ev[4], s));
+    HIP_CHECK(hipEventRecord(rd->ev[4], s));
     if (taken) {
-        SCAN_CHECK(hipMemcpyAsync(data, rd->d_page, bytes,
-                                  hipMemcpyDeviceToHost, s));
-        SCAN_CHECK(hipMemcpyAsync(index, d_oidx, taken * 16,
-                                  hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(data, rd->d_page, bytes,
+                                 hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(index, d_oidx, taken * 16,
+                                 hipMemcpyDeviceToHost, s));
         if (sc->n_ranges && range_ids)
-            SCAN_CHECK(hipMemcpyAsync(range_ids, d_rido, taken * 4,
-                                      hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipMemcpyAsync(range_ids, d_rido, taken * 4,
+                                     hipMemcpyDeviceToHost, s));
     }
-    SCAN_CHECK(hipEventRecord(rd->ev[5], s));
-    SCAN_CHECK(hipStreamSynchronize(s));
-    SCAN_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(rd->ev[5], s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipGetLastError());
+    float ms[5] = {};
     for (int i = 0; i < 5; i++)
-        SCAN_CHECK(hipEventElapsedTime(&ms[i], rd->ev[i], rd->ev[i + 1]));
+        HIP_CHECK(hipEventElapsedTime(&ms[i], rd->ev[i], rd->ev[i + 1]));
     sc->cursor += next;
     page->data_len = bytes;
     page->n_entries = taken;
@@ -4408,12 +4256,8 @@ extern "C" int dbeel_gpu_reader_scan_next(dbeel_gpu_reader_scan* sc,
     page->emit_ms = ms[1];
     page->copy_ms = ms[2];
     page->d2h_ms = ms[4];
-done:
-    /* nothing of this page may still be in flight into the caller's
-     * buffers or the shared scratch */
-    if (rc != DBEEL_OK) (void)hipStreamSynchronize(s);
-    return rc;
-#undef SCAN_CHECK
+    sync_on_fail.dismiss();
+    return DBEEL_OK;
 }
 
 extern "C" int dbeel_gpu_compact_timed(const dbeel_run_view* runs,
@@ -4474,8 +4318,8 @@ static inline const uint8_t* host_entry_key(const dbeel_run_view* run,
     memcpy(&full_size, rec + 12, 4);
     if (key_size < 8 || full_size < 32 ||
         (uint64_t)key_size + 24 > full_size ||
-        off + full_size > run->data_len)
-        return NULL;
+        off > run->data_len || full_size > run->data_len - off)
+        return NULL; /* load_entry's test, equally wrap-proof */
     *klen = key_size - 8;
     return run->data + off + 8;
 }
@@ -4492,10 +4336,8 @@ extern "C" int dbeel_gpu_compact_sliced(const dbeel_run_view* runs,
     }
     int rc = validate_runs(runs, n_runs);
     if (rc) return rc;
-    if (device < 0) {
-        set_err("device must be >= 0 (no CPU fallback)");
-        return DBEEL_ERR_INVALID_ARG;
-    }
+    rc = check_device_arg(device);
+    if (rc) return rc;
     uint64_t total_input = 0, max_count = 0;
     size_t big_run = 0;
     for (size_t r = 0; r < n_runs; r++) {

@@ -123,6 +123,35 @@ def test_corrupt_input_rejected(engine):
     assert ei.value.code == 2
 
 
+@pytest.mark.parametrize("path", ["compact", "ingest", "scan"])
+def test_offset_wraps_rejected(engine, path):
+    """An index record whose offset is 2^64 - 16 makes off + full_size wrap
+    to a small number. The record edit of test_reader_gpu.py's
+    `offset_wraps` case, on the compaction side: load_entry has to reject
+    it before anything is read through it, on every path that runs ahead
+    of the host's look at the error flag."""
+    import struct
+
+    from dbeel_amd.engine import DbeelGpuError, scan
+
+    good = build_run([Entry(b"key-%03d" % i, b"value-%d" % i, 1)
+                      for i in range(200)])
+    far = bytearray(good[1])
+    struct.pack_into("<Q", far, 16 * 199, 2**64 - 16)
+    bad = (good[0], bytes(far))
+    other = build_run([Entry(b"key-%03d" % i, b"other", 2)
+                       for i in range(0, 200, 3)])
+    with pytest.raises(DbeelGpuError) as ei:
+        if path == "compact":
+            engine.compact([other, bad], keep_tombstones=True, device=0)
+        elif path == "ingest":
+            with engine.Job([other, good], device=0) as job:
+                job.ingest([other, bad])
+        else:
+            scan([other, bad], start_key=b"key-100", device=0)
+    assert ei.value.code == 2  # CORRUPT
+
+
 def test_full_cfg3_exact_parity(engine):
     """FULL BASELINE config 3 (8 x 1 GiB runs, 50% overlap, 5% tombstones):
     exact byte parity of the 6.1 GB output vs the CPU oracle, plus the
