@@ -15,6 +15,7 @@ from .engine import (  # noqa: F401
     compact,
     compact_sliced,
     encode_run,
+    flush_batch,
     lookup,
     lookup_raw,
     pin_host,
@@ -25,5 +26,5 @@ from .engine import (  # noqa: F401
 __all__ = [
     "compact", "compact_sliced", "scan", "lookup", "encode_run",
     "Job", "BatchJob", "pin_host", "unpin_host", "DbeelGpuError", "format",
-    "Reader", "lookup_raw",
+    "Reader", "lookup_raw", "flush_batch",
 ]

@@ -52,6 +52,12 @@
  *                  + filter bits in one pass) for the live table list;
  *                  k_reader_scan_bounds/_flag/_emit page the migration
  *                  scan over the resident tables into caller buffers.
+ *   k_batch_*    : the memtable + flush for the reader: an unsorted
+ *                  write batch is ordered (one rocPRIM merge sort on
+ *                  (prefix, key, arrival); or a radix sort on the prefix
+ *                  plus a merge sort of the prefix-tied writes only),
+ *                  deduplicated (last arrival wins) and encoded through
+ *                  the arrival index straight into a new resident table.
  *   host side   : resident jobs, batched independent jobs (one launch
  *                  set, per-job output slicing), streamed pinned ingest
  *                  with copy/compute overlap, sliced compaction for
@@ -2389,6 +2395,14 @@ extern "C" int dbeel_gpu_job_run(dbeel_gpu_job* job, int keep_tombstones,
 /* with a splitmix64 finalizer, identical to dbeel_lsm.cpp's checker. */
 /* ------------------------------------------------------------------ */
 
+/* The filter parameters every device-built "DBLM" shares: sized for 1% fp
+ * (BLOOM_MAX_ALLOWED_ERROR, lsm_tree.rs:48) at k = 7. */
+#define BLOOM_K 7u
+#define BLOOM_SEED 0xDBEE1ull
+static inline uint64_t bloom_bits_for(uint64_t n_keys) {
+    return (uint64_t)(9.585 * (double)(n_keys ? n_keys : 1)) + 64;
+}
+
 /* splitmix64 finalizer */
 __device__ __forceinline__ uint64_t d_mix64(uint64_t h) {
     h ^= h >> 30;
@@ -2438,9 +2452,7 @@ extern "C" int dbeel_gpu_job_bloom(dbeel_gpu_job* job, uint8_t** out_bytes,
         return DBEEL_ERR_INVALID_ARG;
     }
     HIP_CHECK(hipSetDevice(job->device));
-    uint64_t n = job->out_entries ? job->out_entries : 1;
-    /* sizing for 1% fp (BLOOM_MAX_ALLOWED_ERROR, lsm_tree.rs:48) */
-    uint64_t n_bits = (uint64_t)(9.585 * (double)n) + 64;
+    uint64_t n_bits = bloom_bits_for(job->out_entries);
     uint64_t n_words = (n_bits + 31) / 32;
     uint32_t* d_bits = nullptr;
     HIP_CHECK(hipMalloc(&d_bits, n_words * 4));
@@ -2449,7 +2461,7 @@ extern "C" int dbeel_gpu_job_bloom(dbeel_gpu_job* job, uint8_t** out_bytes,
         hipLaunchKernelGGL(k_bloom, dim3(pick_grid(job->out_entries, 256)),
                            dim3(256), 0, job->stream, job->d_outdata,
                            job->d_outindex, job->out_entries, n_bits,
-                           (uint64_t)0xDBEE1, 7u, d_bits);
+                           (uint64_t)BLOOM_SEED, BLOOM_K, d_bits);
     /* "DBLM" | ver | k | pad | n_bits | seed | bitmap (dbeel_lsm.h) */
     uint64_t blen = 32 + ((n_bits + 7) / 8);
     uint8_t* buf = (uint8_t*)calloc(1, blen + 4);
@@ -2459,12 +2471,12 @@ extern "C" int dbeel_gpu_job_bloom(dbeel_gpu_job* job, uint8_t** out_bytes,
         return DBEEL_ERR_OOM;
     }
     memcpy(buf, "DBLM", 4);
-    uint32_t ver = 1, kk = 7, pad = 0;
+    uint32_t ver = 1, kk = BLOOM_K, pad = 0;
     memcpy(buf + 4, &ver, 4);
     memcpy(buf + 8, &kk, 4);
     memcpy(buf + 12, &pad, 4);
     memcpy(buf + 16, &n_bits, 8);
-    uint64_t seed = 0xDBEE1;
+    uint64_t seed = BLOOM_SEED;
     memcpy(buf + 24, &seed, 8);
     hipError_t e = hipMemcpyAsync(buf + 32, d_bits, (n_bits + 7) / 8,
                                   hipMemcpyDeviceToHost, job->stream);
@@ -3260,6 +3272,58 @@ __global__ void k_reader_adopt(const uint8_t* data, const uint8_t* index,
     }
 }
 
+/* Enqueues k_reader_adopt over a table whose run bytes are (being) written
+ * on stream s: prefixes always, and with n_bits != 0 (the table was
+ * allocated with that many) its zeroed-then-set filter bits. */
+static hipError_t table_adopt(ReaderTable& t, uint64_t n_bits, hipStream_t s) {
+    hipError_t e = hipSuccess;
+    if (n_bits) {
+        t.bloom.n_bits = n_bits;
+        t.bloom.seed = BLOOM_SEED;
+        t.bloom.k = BLOOM_K;
+        t.bloom.bits = t.d_bits;
+        e = hipMemsetAsync(t.d_bits, 0, bitmap_bytes(n_bits), s);
+    }
+    if (e == hipSuccess && t.count)
+        hipLaunchKernelGGL(k_reader_adopt, dim3(pick_grid(t.count, 256)),
+                           dim3(256), 0, s, t.data(), t.index(), t.count,
+                           t.d_pfx, (uint32_t*)t.d_bits, n_bits,
+                           (uint64_t)BLOOM_SEED, BLOOM_K);
+    return e;
+}
+
+/* A table's filter as the "DBLM" file dbeel_gpu_job_bloom returns for the
+ * same run: magic | ver | k | pad | n_bits | seed | bitmap. Engine-allocated
+ * (dbeel_gpu_bloom_free); synchronises s. */
+static int table_bloom_fetch(const ReaderTable& t, hipStream_t s,
+                             uint8_t** out_bytes, uint64_t* out_len) {
+    const uint64_t n_bits = t.bloom.n_bits;
+    const uint64_t blen = 32 + (n_bits + 7) / 8;
+    uint8_t* buf = (uint8_t*)calloc(1, blen + 4);
+    if (!buf) {
+        set_err("host alloc failed");
+        return DBEEL_ERR_OOM;
+    }
+    const uint32_t ver = 1, kk = t.bloom.k, pad = 0;
+    memcpy(buf, "DBLM", 4);
+    memcpy(buf + 4, &ver, 4);
+    memcpy(buf + 8, &kk, 4);
+    memcpy(buf + 12, &pad, 4);
+    memcpy(buf + 16, &n_bits, 8);
+    memcpy(buf + 24, &t.bloom.seed, 8);
+    hipError_t e = hipMemcpyAsync(buf + 32, t.d_bits, (n_bits + 7) / 8,
+                                  hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        free(buf);
+        set_err("filter D2H failed: %s", hipGetErrorString(e));
+        return DBEEL_ERR_HIP;
+    }
+    *out_bytes = buf;
+    *out_len = blen;
+    return DBEEL_OK;
+}
+
 extern "C" int dbeel_gpu_reader_compact_begin(
     dbeel_gpu_reader* rd, const uint32_t* positions, size_t n_positions,
     int keep_tombstones, int build_bloom, dbeel_compact_result* out,
@@ -3315,17 +3379,12 @@ extern "C" int dbeel_gpu_reader_compact_begin(
     }
 
     /* output -> right-sized resident table, device to device */
-    const uint64_t n_bits =
-        build_bloom
-            ? (uint64_t)(9.585 * (double)(out_entries ? out_entries : 1)) + 64
-            : 0;
-    const uint64_t seed = 0xDBEE1;
+    const uint64_t n_bits = build_bloom ? bloom_bits_for(out_entries) : 0;
     ReaderTable t;
     hipStream_t s = job->stream;
     hipError_t e = table_alloc(t, out_data_len, out_entries, n_bits);
     float adopt_ms = 0, d2h_ms = 0;
     uint64_t d2h_bytes = 0;
-    uint8_t* bbuf = nullptr;
     if (e == hipSuccess) e = hipEventRecord(job->ev[0], s);
     if (e == hipSuccess && out_data_len)
         e = hipMemcpyAsync(t.d_run + 16, job->d_outdata, out_data_len,
@@ -3333,17 +3392,7 @@ extern "C" int dbeel_gpu_reader_compact_begin(
     if (e == hipSuccess && out_entries)
         e = hipMemcpyAsync(t.d_run + 16 + out_data_len, job->d_outindex,
                            out_entries * 16, hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess && n_bits) {
-        t.bloom.n_bits = n_bits;
-        t.bloom.seed = seed;
-        t.bloom.k = 7;
-        t.bloom.bits = t.d_bits;
-        e = hipMemsetAsync(t.d_bits, 0, bitmap_bytes(n_bits), s);
-    }
-    if (e == hipSuccess && out_entries)
-        hipLaunchKernelGGL(k_reader_adopt, dim3(pick_grid(out_entries, 256)),
-                           dim3(256), 0, s, t.data(), t.index(), out_entries,
-                           t.d_pfx, (uint32_t*)t.d_bits, n_bits, seed, 7u);
+    if (e == hipSuccess) e = table_adopt(t, n_bits, s);
     if (e == hipSuccess) e = hipEventRecord(job->ev[1], s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e == hipSuccess) e = hipGetLastError();
@@ -3364,34 +3413,9 @@ extern "C" int dbeel_gpu_reader_compact_begin(
             d2h_bytes += out->data_len + out->index_len;
         }
         if (bloom_bytes && n_bits) {
-            /* "DBLM" | ver | k | pad | n_bits | seed | bitmap — the bytes
-             * dbeel_gpu_job_bloom returns for the same output */
-            const uint64_t blen = 32 + (n_bits + 7) / 8;
-            bbuf = (uint8_t*)calloc(1, blen + 4);
-            if (!bbuf) {
-                set_err("host alloc failed");
-                rc = DBEEL_ERR_OOM;
-                goto fail;
-            }
-            const uint32_t ver = 1, kk = 7, pad = 0;
-            memcpy(bbuf, "DBLM", 4);
-            memcpy(bbuf + 4, &ver, 4);
-            memcpy(bbuf + 8, &kk, 4);
-            memcpy(bbuf + 12, &pad, 4);
-            memcpy(bbuf + 16, &n_bits, 8);
-            memcpy(bbuf + 24, &seed, 8);
-            e = hipMemcpyAsync(bbuf + 32, t.d_bits, (n_bits + 7) / 8,
-                               hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess) {
-                set_err("filter D2H failed: %s", hipGetErrorString(e));
-                rc = DBEEL_ERR_HIP;
-                goto fail;
-            }
+            rc = table_bloom_fetch(t, s, bloom_bytes, bloom_len);
+            if (rc) goto fail;
             d2h_bytes += (n_bits + 7) / 8;
-            *bloom_bytes = bbuf;
-            *bloom_len = blen;
-            bbuf = nullptr;
         }
         (void)hipEventRecord(job->ev[3], s);
         (void)hipEventSynchronize(job->ev[3]);
@@ -3416,7 +3440,6 @@ fail:
     (void)hipStreamSynchronize(s);
     dbeel_gpu_job_destroy(job);
     table_free(t);
-    free(bbuf);
     if (out) dbeel_gpu_result_free(out);
     if (bloom_bytes && *bloom_bytes) {
         free(*bloom_bytes);
@@ -3462,6 +3485,671 @@ extern "C" int dbeel_gpu_reader_compact_commit(dbeel_gpu_reader* rd,
     /* reader_link leaves the stream idle: nothing reads the old tables */
     hipError_t e = reader_link(rd);
     for (ReaderTable& t : gone) table_free(t);
+    HIP_CHECK(e);
+    return DBEEL_OK;
+}
+
+/* ------------------------------------------------------------------ */
+/* Write batch: the memtable flush on the device                      */
+/*                                                                    */
+/* The reference's memtable is a red-black tree whose set() replaces  */
+/* the value of an equal key whatever the timestamps are              */
+/* (rbtree_arena/src/lib.rs:497-511); flush iterates it in key order  */
+/* into EntryWriter and pushes the table onto the sstable list with   */
+/* no bloom (lsm_tree.rs:882-915, 925-946). Here the writes arrive in */
+/* arrival order, unsorted, with repeated keys:                       */
+/*   k_batch_prefix : per write, big-endian 8-B key prefix + arrival  */
+/*                    index.                                          */
+/*   order          : two paths, chosen by DBEEL_BATCH_ORDER (read on */
+/*                    every call). "radix": stable rocPRIM radix sort */
+/*                    on (prefix, arrival), then only the writes whose*/
+/*                    prefix equals a neighbour's are compacted,      */
+/*                    merge-sorted by (prefix, key bytes past 8 and   */
+/*                    length, arrival) and scattered back — no walk,  */
+/*                    nothing quadratic when every key shares its     */
+/*                    first 8 bytes. "merge" (the default, the faster */
+/*                    one as measured): one merge sort over all pairs */
+/*                    with the same comparator.                       */
+/*   k_batch_flag   : equal keys are now adjacent in arrival order;   */
+/*                    the last of each group survives. Emits RankRecs */
+/*                    so survivor_scans gives positions and offsets.  */
+/*   k_batch_totals : {bytes, survivors} for the host's one read,     */
+/*                    which sizes the output.                         */
+/*   k_batch_encode : wave per survivor, gathered through the arrival */
+/*                    index from the staged blobs straight into the   */
+/*                    output (a new resident table's allocation, or a */
+/*                    plain buffer), index records included.          */
+/* ------------------------------------------------------------------ */
+
+struct BatchIn {
+    uint64_t n;
+    const uint8_t* keys;
+    const uint64_t* koff;
+    const uint8_t* vals;
+    const uint64_t* voff;
+    const uint8_t* ts;
+};
+
+/* One (prefix, arrival) pair as the merge sort moves it. */
+struct BatchPair {
+    uint64_t pfx;
+    uint32_t arr;
+    uint32_t rsv;
+};
+
+/* The staged key blob, for compares by arrival index. */
+struct BatchKeys {
+    const uint8_t* keys;
+    const uint64_t* koff;
+    uint32_t n;
+};
+
+/* Order of two writes whose 8-byte prefixes are EQUAL: when both keys are
+ * longer than 8 bytes, cmp_keys on the bytes past them; otherwise the
+ * shorter key is a prefix of the other (the prefix is zero-padded), so the
+ * lengths decide. */
+__device__ __forceinline__ int batch_cmp_tied(const BatchKeys& K, uint32_t a,
+                                              uint32_t b) {
+    const uint64_t oa = K.koff[a], la = K.koff[a + 1] - oa;
+    const uint64_t ob = K.koff[b], lb = K.koff[b + 1] - ob;
+    if (la > 8 && lb > 8)
+        return cmp_keys(K.keys + oa + 8, la - 8, K.keys + ob + 8, lb - 8);
+    return la < lb ? -1 : (la > lb ? 1 : 0);
+}
+
+/* prefix, then key, then arrival. A pair whose arrival index is not below
+ * n is no write of this batch (a sort may hand the comparator padding): it
+ * is never dereferenced and orders after every real pair. */
+struct BatchLess {
+    BatchKeys K;
+    __device__ bool operator()(const BatchPair& a, const BatchPair& b) const {
+        if (a.arr >= K.n || b.arr >= K.n) return a.arr < b.arr;
+        if (a.pfx != b.pfx) return a.pfx < b.pfx;
+        const int c = batch_cmp_tied(K, a.arr, b.arr);
+        return c ? c < 0 : a.arr < b.arr;
+    }
+};
+
+__global__ void k_batch_prefix(BatchKeys K, uint64_t* pfx, uint32_t* arr) {
+    uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < K.n;
+         i += stride) {
+        const uint64_t o = K.koff[i];
+        pfx[i] = key_prefix(K.keys + o, K.koff[i + 1] - o);
+        arr[i] = i;
+    }
+}
+
+/* tie[i] = 1 iff sorted prefix i equals a neighbour's. */
+__global__ void k_batch_tieflag(uint32_t n, const uint64_t* pfx,
+                                uint32_t* tie) {
+    uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += stride) {
+        const uint64_t p = pfx[i];
+        tie[i] = ((i && pfx[i - 1] == p) || (i + 1 < n && pfx[i + 1] == p))
+                     ? 1u : 0u;
+    }
+}
+
+/* Gathers the flagged (tie == NULL: all) pairs into a dense list, and puts
+ * a sorted list back into the same positions in ascending order. */
+__global__ void k_batch_pairs(uint32_t n, const uint64_t* pfx,
+                              const uint32_t* arr, const uint32_t* tie,
+                              const uint32_t* tpos, BatchPair* out) {
+    uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += stride) {
+        if (tie && !tie[i]) continue;
+        BatchPair p = {pfx[i], arr[i], 0};
+        out[tie ? tpos[i] : i] = p;
+    }
+}
+
+__global__ void k_batch_unpairs(uint32_t n, const BatchPair* in,
+                                const uint32_t* tie, const uint32_t* tpos,
+                                uint64_t* pfx, uint32_t* arr) {
+    uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += stride) {
+        if (tie && !tie[i]) continue;
+        const BatchPair p = in[tie ? tpos[i] : i];
+        pfx[i] = p.pfx;
+        arr[i] = p.arr;
+    }
+}
+
+/* Sorted write i survives iff it is the last one or its key differs from
+ * its successor's (equal keys are adjacent, in arrival order: the last
+ * arrival wins). src = keep flag | arrival index. */
+__global__ void k_batch_flag(BatchKeys K, const uint64_t* pfx,
+                             const uint32_t* arr, const uint64_t* voff,
+                             RankRec* rrec) {
+    uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < K.n;
+         i += stride) {
+        const uint32_t a = arr[i];
+        const uint64_t klen = K.koff[a + 1] - K.koff[a];
+        const uint64_t vlen = voff[a + 1] - voff[a];
+        const bool keep = i + 1 == K.n || pfx[i] != pfx[i + 1] ||
+                          batch_cmp_tied(K, a, arr[i + 1]) != 0;
+        RankRec r;
+        r.src = (keep ? RR_KEEP : 0) | a;
+        r.key_size = (uint32_t)(8 + klen);
+        r.full_size = (uint32_t)(32 + klen + vlen);
+        rrec[i] = r;
+    }
+}
+
+__global__ void k_batch_totals(const RankRec* rrec, const uint64_t* dst_off,
+                               const uint32_t* pos, uint32_t n,
+                               const uint32_t* zero, StepTotals* tot) {
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        store_totals(tot, zero, rrec[n - 1], dst_off[n - 1], pos[n - 1]);
+}
+
+__global__ void k_batch_encode(uint32_t n, const RankRec* rrec,
+                               const uint64_t* dst_off, const uint32_t* pos,
+                               const uint8_t* keys, const uint64_t* koff,
+                               const uint8_t* vals, const uint64_t* voff,
+                               const uint8_t* ts, uint8_t* out_data,
+                               uint8_t* out_index) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
+    for (uint32_t i = wave; i < n; i += n_waves) {
+        const RankRec r = rrec[i];
+        if (!(r.src & RR_KEEP)) continue;
+        const uint32_t a = (uint32_t)r.src;
+        const uint64_t klen = r.key_size - 8;
+        const uint64_t vlen = (uint64_t)r.full_size - 32 - klen;
+        const uint64_t off = dst_off[i];
+        uint8_t* dst = out_data + off;
+        if (lane == 0) {
+            __builtin_memcpy(dst, &klen, 8);
+            __builtin_memcpy(dst + 8 + klen, &vlen, 8);
+            __builtin_memcpy(dst + 16 + klen + vlen, ts + (uint64_t)a * 16,
+                             16);
+            uint8_t* rec = out_index + (uint64_t)pos[i] * 16;
+            __builtin_memcpy(rec, &off, 8);
+            __builtin_memcpy(rec + 8, &r.key_size, 4);
+            __builtin_memcpy(rec + 12, &r.full_size, 4);
+        }
+        wave_copy_bytes(dst + 8, keys + koff[a], klen, lane);
+        wave_copy_bytes(dst + 16 + klen, vals + voff[a], vlen, lane);
+    }
+}
+
+/* What both entry points ask of the arrays, on the host. */
+static int batch_check_arrays(const char* who, const BatchIn& in) {
+    if (in.n && (!in.keys || !in.koff || !in.vals || !in.voff || !in.ts)) {
+        set_err("%s: null array", who);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    return DBEEL_OK;
+}
+
+/* 2^31 writes or more (arrival indices and the kernels' loop counters are
+ * u32, and a counter plus one grid stride must not wrap) and a descending
+ * offset are DBEEL_ERR_INVALID_ARG at once; *too_large
+ * receives the first write with 32 + klen + vlen > u32::MAX, n when there
+ * is none (error.rs:60-61), for the caller to report after its own checks. */
+static int batch_check_offsets(const char* who, const BatchIn& in,
+                               uint64_t* too_large) {
+    *too_large = in.n;
+    if (in.n >= (1ull << 31)) {
+        set_err("%s: %llu writes, at most 2^31 - 1 per batch", who,
+                (unsigned long long)in.n);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    for (uint64_t i = 0; i < in.n; i++) {
+        if (in.koff[i + 1] < in.koff[i] || in.voff[i + 1] < in.voff[i]) {
+            set_err("%s: offsets of write %llu descend", who,
+                    (unsigned long long)i);
+            return DBEEL_ERR_INVALID_ARG;
+        }
+        const uint64_t klen = in.koff[i + 1] - in.koff[i];
+        const uint64_t vlen = in.voff[i + 1] - in.voff[i];
+        if (*too_large == in.n && (klen > 0xFFFFFFFFull ||
+                                   vlen > 0xFFFFFFFFull ||
+                                   32 + klen + vlen > 0xFFFFFFFFull))
+            *too_large = i;
+    }
+    return DBEEL_OK;
+}
+
+static int batch_too_large(const char* who, uint64_t i) {
+    set_err("%s: write %llu is larger than u32::MAX bytes encoded", who,
+            (unsigned long long)i);
+    return DBEEL_ERR_ITEM_TOO_LARGE;
+}
+
+/* Device staging and scratch of ONE call; the call frees it. */
+struct BatchStage {
+    uint8_t* d_slab = nullptr;    /* everything sized by the input alone   */
+    void* d_tmp = nullptr;        /* rocPRIM scratch: radix sort and scans */
+    BatchPair* d_pairs = nullptr; /* merge sort: pairs in | pairs out      */
+    void* d_mtmp = nullptr;       /* merge sort scratch                    */
+    struct Host {
+        StepTotals tot;
+        uint32_t tie_pos, tie_flag; /* of the last write: their sum is the
+                                       tied count */
+    }* h = nullptr;               /* pinned                                */
+    /* carved out of d_slab */
+    uint8_t *keys, *vals, *ts;
+    uint64_t *koff, *voff, *pfx[2];
+    uint32_t *arr[2], *tie, *tpos, *zero;
+    RankRec* rrec;
+    StepTotals* tot;
+    int cur = 0;                  /* pfx[cur] / arr[cur] hold the order    */
+    uint64_t* dst_off() const { return pfx[cur ^ 1]; } /* free after order */
+    uint32_t* pos() const { return tie; }              /* free after order */
+    uint32_t n = 0;
+    uint64_t n_surv = 0, total_bytes = 0, prefix_tied = 0;
+};
+
+static void batch_release(BatchStage& b) {
+    (void)hipFree(b.d_slab);
+    (void)hipFree(b.d_tmp);
+    (void)hipFree(b.d_pairs);
+    (void)hipFree(b.d_mtmp);
+    if (b.h) (void)hipHostFree(b.h);
+    b = BatchStage();
+}
+
+/* merge-sorts m pairs of b.d_pairs[0..m) into b.d_pairs[m..2m). */
+static int batch_merge_sort(BatchStage& b, uint64_t m, hipStream_t s) {
+    const BatchLess less = {{b.keys, b.koff, b.n}};
+    size_t bytes = 0;
+    HIP_CHECK(rocprim::merge_sort(nullptr, bytes, b.d_pairs, b.d_pairs + m, m,
+                                  less, s));
+    HIP_CHECK(hipMalloc(&b.d_mtmp, bytes ? bytes : 1));
+    HIP_CHECK(rocprim::merge_sort(b.d_mtmp, bytes, b.d_pairs, b.d_pairs + m,
+                                  m, less, s));
+    return DBEEL_OK;
+}
+
+/* Steps 1-4 on stream s: upload, prefixes, order, survivor flags and
+ * scans; returns with the stream idle and n_surv / total_bytes /
+ * prefix_tied known to the host. ev (NULL or 3 events) receives the marks
+ * start | uploaded | ordered. The input was validated: in.n in [1, 2^31). */
+static int batch_order(BatchStage& b, const BatchIn& in, hipStream_t s,
+                       hipEvent_t* ev) {
+    const uint32_t n = b.n = (uint32_t)in.n;
+    const uint64_t kbytes = in.koff[n], vbytes = in.voff[n];
+    /* measured: the single merge sort is the faster of
+     * the two on three of the four benchmark shapes, so it is the default */
+    const char* mode = getenv("DBEEL_BATCH_ORDER");
+    const bool merge_all = !(mode && strcmp(mode, "radix") == 0);
+
+    /* the slab: 16-B aligned pieces */
+    uint64_t at = 0;
+    auto carve = [&](uint64_t bytes) {
+        const uint64_t o = at;
+        at += (bytes + 15) & ~15ull;
+        return o;
+    };
+    const uint64_t o_keys = carve(kbytes), o_vals = carve(vbytes),
+                   o_ts = carve((uint64_t)n * 16),
+                   o_koff = carve((uint64_t)(n + 1) * 8),
+                   o_voff = carve((uint64_t)(n + 1) * 8),
+                   o_pfx0 = carve((uint64_t)n * 8),
+                   o_pfx1 = carve((uint64_t)n * 8),
+                   o_arr0 = carve((uint64_t)n * 4),
+                   o_arr1 = carve((uint64_t)n * 4),
+                   o_tie = carve((uint64_t)n * 4),
+                   o_tpos = carve((uint64_t)n * 4),
+                   o_rrec = carve((uint64_t)n * sizeof(RankRec)),
+                   o_tot = carve(sizeof(StepTotals)), o_zero = carve(16);
+    HIP_CHECK(hipMalloc(&b.d_slab, at));
+    HIP_CHECK(hipHostMalloc(&b.h, sizeof *b.h));
+    uint8_t* S = b.d_slab;
+    b.keys = S + o_keys;
+    b.vals = S + o_vals;
+    b.ts = S + o_ts;
+    b.koff = (uint64_t*)(S + o_koff);
+    b.voff = (uint64_t*)(S + o_voff);
+    b.pfx[0] = (uint64_t*)(S + o_pfx0);
+    b.pfx[1] = (uint64_t*)(S + o_pfx1);
+    b.arr[0] = (uint32_t*)(S + o_arr0);
+    b.arr[1] = (uint32_t*)(S + o_arr1);
+    b.tie = (uint32_t*)(S + o_tie);
+    b.tpos = (uint32_t*)(S + o_tpos);
+    b.rrec = (RankRec*)(S + o_rrec);
+    b.tot = (StepTotals*)(S + o_tot);
+    b.zero = (uint32_t*)(S + o_zero);
+
+    /* one scratch buffer for the primitives whose size n alone decides */
+    size_t t_radix = 0, t_scan = 0, t_surv = 0;
+    HIP_CHECK(rocprim::radix_sort_pairs(nullptr, t_radix, b.pfx[0], b.pfx[1],
+                                        b.arr[0], b.arr[1], n, 0, 64, s));
+    HIP_CHECK(rocprim::exclusive_scan(nullptr, t_scan, b.tie, b.tpos,
+                                      (uint32_t)0, n,
+                                      rocprim::plus<uint32_t>(), s));
+    HIP_CHECK(survivor_scans(nullptr, t_surv, b.rrec, b.pfx[0], b.tie, n, s));
+    size_t tmp_bytes = t_radix > t_scan ? t_radix : t_scan;
+    if (t_surv > tmp_bytes) tmp_bytes = t_surv;
+    HIP_CHECK(hipMalloc(&b.d_tmp, tmp_bytes ? tmp_bytes : 1));
+
+    /* 1. upload */
+    if (ev) HIP_CHECK(hipEventRecord(ev[0], s));
+    if (kbytes)
+        HIP_CHECK(hipMemcpyAsync(b.keys, in.keys, kbytes,
+                                 hipMemcpyHostToDevice, s));
+    if (vbytes)
+        HIP_CHECK(hipMemcpyAsync(b.vals, in.vals, vbytes,
+                                 hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(b.ts, in.ts, (uint64_t)n * 16,
+                             hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(b.koff, in.koff, (uint64_t)(n + 1) * 8,
+                             hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(b.voff, in.voff, (uint64_t)(n + 1) * 8,
+                             hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemsetAsync(b.zero, 0, 16, s));
+    if (ev) HIP_CHECK(hipEventRecord(ev[1], s));
+
+    /* 2. prefixes, 3. order */
+    const BatchKeys K = {b.keys, b.koff, n};
+    const dim3 grid(pick_grid(n, 256)), block(256);
+    hipLaunchKernelGGL(k_batch_prefix, grid, block, 0, s, K, b.pfx[0],
+                       b.arr[0]);
+    if (merge_all) {
+        HIP_CHECK(hipMalloc(&b.d_pairs, 2ull * n * sizeof(BatchPair)));
+        hipLaunchKernelGGL(k_batch_pairs, grid, block, 0, s, n, b.pfx[0],
+                           b.arr[0], (const uint32_t*)nullptr,
+                           (const uint32_t*)nullptr, b.d_pairs);
+        int rc = batch_merge_sort(b, n, s);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_batch_unpairs, grid, block, 0, s, n,
+                           b.d_pairs + n, (const uint32_t*)nullptr,
+                           (const uint32_t*)nullptr, b.pfx[0], b.arr[0]);
+        b.cur = 0;
+    } else {
+        size_t tb = tmp_bytes;
+        HIP_CHECK(rocprim::radix_sort_pairs(b.d_tmp, tb, b.pfx[0], b.pfx[1],
+                                            b.arr[0], b.arr[1], n, 0, 64, s));
+        b.cur = 1;
+    }
+    /* the equal-prefix stretches: flag, count (= prefix_tied) */
+    uint64_t* pfx = b.pfx[b.cur];
+    uint32_t* arr = b.arr[b.cur];
+    hipLaunchKernelGGL(k_batch_tieflag, grid, block, 0, s, n, pfx, b.tie);
+    {
+        size_t tb = tmp_bytes;
+        HIP_CHECK(rocprim::exclusive_scan(b.d_tmp, tb, b.tie, b.tpos,
+                                          (uint32_t)0, n,
+                                          rocprim::plus<uint32_t>(), s));
+    }
+    HIP_CHECK(hipMemcpyAsync(&b.h->tie_pos, b.tpos + (n - 1), 4,
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(&b.h->tie_flag, b.tie + (n - 1), 4,
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipGetLastError());
+    const uint64_t m = b.prefix_tied = (uint64_t)b.h->tie_pos + b.h->tie_flag;
+    if (m > n) {
+        set_err("write batch: tied count %llu exceeds the %u writes",
+                (unsigned long long)m, n);
+        return DBEEL_ERR_HIP;
+    }
+    if (m && !merge_all) {
+        /* settle them: compact, merge sort, scatter back in place */
+        HIP_CHECK(hipMalloc(&b.d_pairs, 2 * m * sizeof(BatchPair)));
+        hipLaunchKernelGGL(k_batch_pairs, grid, block, 0, s, n, pfx, arr,
+                           b.tie, b.tpos, b.d_pairs);
+        int rc = batch_merge_sort(b, m, s);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_batch_unpairs, grid, block, 0, s, n,
+                           b.d_pairs + m, b.tie, b.tpos, pfx, arr);
+    }
+    if (ev) HIP_CHECK(hipEventRecord(ev[2], s));
+
+    /* 4. survivors: flags, positions, byte offsets, totals */
+    hipLaunchKernelGGL(k_batch_flag, grid, block, 0, s, K, pfx, arr, b.voff,
+                       b.rrec);
+    {
+        size_t tb = tmp_bytes;
+        HIP_CHECK(survivor_scans(b.d_tmp, tb, b.rrec, b.dst_off(), b.pos(), n,
+                                 s));
+    }
+    hipLaunchKernelGGL(k_batch_totals, dim3(1), dim3(64), 0, s, b.rrec,
+                       b.dst_off(), b.pos(), n, b.zero, b.tot);
+    HIP_CHECK(hipMemcpyAsync(&b.h->tot, b.tot, sizeof(StepTotals),
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipGetLastError());
+    b.n_surv = b.h->tot.n_surv;
+    b.total_bytes = b.h->tot.total_out;
+    /* what the encode kernel's stores are bounded by */
+    if (b.n_surv == 0 || b.n_surv > n ||
+        b.total_bytes > 32ull * n + kbytes + vbytes ||
+        b.total_bytes < 32 * b.n_surv) {
+        set_err("write batch: survivor totals %llu entries / %llu bytes are "
+                "impossible for %u writes", (unsigned long long)b.n_surv,
+                (unsigned long long)b.total_bytes, n);
+        return DBEEL_ERR_HIP;
+    }
+    return DBEEL_OK;
+}
+
+/* 5. encode into out_data (total_bytes) / out_index (n_surv records). */
+static void batch_encode(const BatchStage& b, hipStream_t s,
+                         uint8_t* out_data, uint8_t* out_index) {
+    hipLaunchKernelGGL(k_batch_encode,
+                       dim3(pick_grid((uint64_t)b.n * 64, 256)), dim3(256), 0,
+                       s, b.n, b.rrec, b.dst_off(), b.pos(), b.keys, b.koff,
+                       b.vals, b.voff, b.ts, out_data, out_index);
+}
+
+/* Engine-allocated host copy of a run lying on the device; synchronises s.
+ * On failure out is left zeroed. */
+static int batch_fetch(const uint8_t* d_data, uint64_t dlen,
+                       const uint8_t* d_index, uint64_t n_entries,
+                       hipStream_t s, dbeel_compact_result* out) {
+    const uint64_t ilen = n_entries * 16;
+    ScopeGuard drop([&] { dbeel_gpu_result_free(out); });
+    out->data = (uint8_t*)malloc(dlen ? dlen : 1);
+    out->index = (uint8_t*)malloc(ilen ? ilen : 1);
+    if (!out->data || !out->index) {
+        set_err("host malloc failed");
+        return DBEEL_ERR_OOM;
+    }
+    if (dlen)
+        HIP_CHECK(hipMemcpyAsync(out->data, d_data, dlen,
+                                 hipMemcpyDeviceToHost, s));
+    if (ilen)
+        HIP_CHECK(hipMemcpyAsync(out->index, d_index, ilen,
+                                 hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    out->data_len = dlen;
+    out->index_len = ilen;
+    out->entries_written = n_entries;
+    drop.dismiss();
+    return DBEEL_OK;
+}
+
+extern "C" int dbeel_gpu_flush_batch(uint64_t n_writes, const uint8_t* keys,
+                                     const uint64_t* key_offsets,
+                                     const uint8_t* values,
+                                     const uint64_t* value_offsets,
+                                     const uint8_t* timestamps, int device,
+                                     dbeel_compact_result* out) {
+    g_err[0] = 0;
+    if (!out) {
+        set_err("flush_batch: out is null");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    memset(out, 0, sizeof *out);
+    const BatchIn in = {n_writes, keys, key_offsets, values, value_offsets,
+                        timestamps};
+    int rc = batch_check_arrays("flush_batch", in);
+    if (rc) return rc;
+    rc = check_device_arg(device);
+    if (rc) return rc;
+    uint64_t too_large = 0;
+    rc = batch_check_offsets("flush_batch", in, &too_large);
+    if (rc) return rc;
+    if (too_large != in.n) return batch_too_large("flush_batch", too_large);
+    if (in.n == 0) return DBEEL_OK; /* an empty memtable flushes nothing */
+    rc = select_device(device);
+    if (rc) return rc;
+
+    BatchStage b;
+    hipStream_t s = nullptr;
+    uint8_t* d_out = nullptr;
+    ScopeGuard release([&] {
+        if (s) (void)hipStreamSynchronize(s);
+        batch_release(b);
+        (void)hipFree(d_out);
+        if (s) (void)hipStreamDestroy(s);
+    });
+    HIP_CHECK(hipStreamCreate(&s));
+    rc = batch_order(b, in, s, nullptr);
+    if (rc) return rc;
+    HIP_CHECK(hipMalloc(&d_out, b.total_bytes + b.n_surv * 16));
+    batch_encode(b, s, d_out, d_out + b.total_bytes);
+    HIP_CHECK(hipGetLastError());
+    return batch_fetch(d_out, b.total_bytes, d_out + b.total_bytes, b.n_surv,
+                       s, out);
+}
+
+extern "C" int dbeel_gpu_reader_write_batch(
+    dbeel_gpu_reader* rd, size_t pos, uint64_t n_writes, const uint8_t* keys,
+    const uint64_t* key_offsets, const uint8_t* values,
+    const uint64_t* value_offsets, const uint8_t* timestamps, int build_bloom,
+    dbeel_compact_result* out, uint8_t** bloom_bytes, uint64_t* bloom_len,
+    dbeel_write_batch_stats* stats) {
+    g_err[0] = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (out) memset(out, 0, sizeof *out);
+    if (bloom_bytes) *bloom_bytes = nullptr;
+    if (bloom_len) *bloom_len = 0;
+    if (!rd) {
+        set_err("reader_write_batch: null reader");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    const BatchIn in = {n_writes, keys, key_offsets, values, value_offsets,
+                        timestamps};
+    int rc = batch_check_arrays("reader_write_batch", in);
+    if (rc) return rc;
+    if (pos > rd->tables.size()) {
+        set_err("reader_write_batch: position %zu past the %zu runs held",
+                pos, rd->tables.size());
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if ((bloom_bytes == nullptr) != (bloom_len == nullptr)) {
+        set_err("reader_write_batch: bloom_bytes and bloom_len go together");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    uint64_t too_large = 0;
+    rc = batch_check_offsets("reader_write_batch", in, &too_large);
+    if (rc) return rc;
+    if (in.n && rd->tables.size() >= MAX_RUNS) {
+        set_err("reader_write_batch: reader already holds %d runs", MAX_RUNS);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (too_large != in.n)
+        return batch_too_large("reader_write_batch", too_large);
+    if (in.n == 0) return DBEEL_OK; /* lsm_tree.rs:850-852 */
+
+    HIP_CHECK(hipSetDevice(rd->device));
+    hipStream_t s = rd->stream;
+    BatchStage b;
+    ReaderTable t;
+    bool linked = false;
+    ScopeGuard release([&] {
+        (void)hipStreamSynchronize(s);
+        batch_release(b);
+        if (linked) return;
+        table_free(t);
+        if (out) dbeel_gpu_result_free(out);
+        if (bloom_bytes && *bloom_bytes) {
+            free(*bloom_bytes);
+            *bloom_bytes = nullptr;
+            *bloom_len = 0;
+        }
+    });
+    rc = batch_order(b, in, s, rd->ev);
+    if (rc) return rc;
+
+    /* 5. encode straight into a right-sized table, 6. adopt it */
+    const uint64_t n_bits = build_bloom ? bloom_bits_for(b.n_surv) : 0;
+    HIP_CHECK(table_alloc(t, b.total_bytes, b.n_surv, n_bits));
+    batch_encode(b, s, t.d_run + 16, t.d_run + 16 + b.total_bytes);
+    HIP_CHECK(hipEventRecord(rd->ev[3], s));
+    HIP_CHECK(table_adopt(t, n_bits, s));
+    HIP_CHECK(hipEventRecord(rd->ev[4], s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipGetLastError());
+
+    /* host copies: what the caller writes to {index}.data/.index/.bloom */
+    uint64_t d2h_bytes = 0;
+    const bool fetched = out || (bloom_bytes && n_bits);
+    if (fetched) {
+        HIP_CHECK(hipEventRecord(rd->ev[5], s));
+        if (out) {
+            rc = batch_fetch(t.data(), t.data_len, t.index(), t.count, s, out);
+            if (rc) return rc;
+            d2h_bytes += out->data_len + out->index_len;
+        }
+        if (bloom_bytes && n_bits) {
+            rc = table_bloom_fetch(t, s, bloom_bytes, bloom_len);
+            if (rc) return rc;
+            d2h_bytes += (n_bits + 7) / 8;
+        }
+        HIP_CHECK(hipEventRecord(rd->ev[6], s));
+        HIP_CHECK(hipEventSynchronize(rd->ev[6]));
+    }
+    dbeel_write_batch_stats st;
+    memset(&st, 0, sizeof st);
+    float ms[5] = {0, 0, 0, 0, 0};
+    for (int i = 0; i < 4; i++)
+        HIP_CHECK(hipEventElapsedTime(&ms[i], rd->ev[i], rd->ev[i + 1]));
+    if (fetched)
+        HIP_CHECK(hipEventElapsedTime(&ms[4], rd->ev[5], rd->ev[6]));
+    st.h2d_ms = ms[0];
+    st.order_ms = ms[1];
+    st.encode_ms = ms[2];
+    st.adopt_ms = ms[3];
+    st.d2h_ms = ms[4];
+    st.writes_in = b.n;
+    st.entries_out = b.n_surv;
+    st.data_bytes_out = b.total_bytes;
+    st.prefix_tied = b.prefix_tied;
+    st.d2h_bytes = d2h_bytes;
+
+    /* the list edit of insert_run; on a failed link the edit is undone */
+    rd->tables.insert(rd->tables.begin() + pos, t);
+    hipError_t e = reader_link(rd);
+    if (e != hipSuccess) {
+        rd->tables.erase(rd->tables.begin() + pos);
+        (void)reader_link(rd);
+        HIP_CHECK(e);
+    }
+    linked = true;
+    rd->generation++; /* open scans are stale from here on */
+    /* a pending compaction keeps naming the same tables */
+    for (uint32_t& p : rd->pending_pos)
+        if (p >= pos) p++;
+    if (stats) *stats = st;
+    return DBEEL_OK;
+}
+
+/* Library-internal (dbeel_lsm.cpp: a flush whose files could not be
+ * written): takes the table at pos out of the list again — the inverse of
+ * the list edit above. */
+extern "C" __attribute__((visibility("hidden"))) int dbeel_reader_drop_run(
+    dbeel_gpu_reader* rd, size_t pos) {
+    if (!rd || pos >= rd->tables.size()) return DBEEL_ERR_INVALID_ARG;
+    HIP_CHECK(hipSetDevice(rd->device));
+    HIP_CHECK(hipStreamSynchronize(rd->stream));
+    ReaderTable t = rd->tables[pos];
+    rd->tables.erase(rd->tables.begin() + pos);
+    rd->generation++;
+    for (uint32_t& p : rd->pending_pos)
+        if (p > pos) p--;
+    hipError_t e = reader_link(rd);
+    table_free(t);
     HIP_CHECK(e);
     return DBEEL_OK;
 }

@@ -530,26 +530,46 @@ extern "C" int dbeel_lsm_compact_tree(const char* dir_c,
 extern "C" uint64_t dbeel_reader_run_data_len(const dbeel_gpu_reader* rd,
                                               size_t pos);
 
-extern "C" int dbeel_lsm_reader_add(const char* dir_c, dbeel_gpu_reader* rd,
-                                    uint64_t* indices, size_t* n,
-                                    uint64_t sstable_index) {
+extern "C" int dbeel_reader_drop_run(dbeel_gpu_reader* rd, size_t pos);
+
+namespace {
+/* Where a new sstable goes in a reader described by indices[0..*n): its
+ * ascending-index position, what a fresh dbeel_lsm_reader_open of the
+ * directory would give it. */
+int new_run_position(const char* dir_c, dbeel_gpu_reader* rd,
+                     const uint64_t* indices, const size_t* n,
+                     uint64_t sstable_index, size_t* pos) {
     if (!dir_c || !rd || !indices || !n) {
-        dbeel_set_last_error("lsm_reader_add: null argument");
+        dbeel_set_last_error("lsm reader: null argument");
         return DBEEL_ERR_INVALID_ARG;
     }
     if (*n != dbeel_gpu_reader_run_count(rd) || *n >= 64) {
-        dbeel_set_last_error("lsm_reader_add: indices do not describe the "
+        dbeel_set_last_error("lsm reader: indices do not describe the "
                              "reader, or it already holds 64 runs");
         return DBEEL_ERR_INVALID_ARG;
     }
-    /* ascending-index position: what a fresh dbeel_lsm_reader_open of the
-     * directory would give this sstable */
-    size_t pos = std::lower_bound(indices, indices + *n, sstable_index) -
-                 indices;
-    if (pos < *n && indices[pos] == sstable_index) {
-        dbeel_set_last_error("lsm_reader_add: sstable already in the reader");
+    *pos = std::lower_bound(indices, indices + *n, sstable_index) - indices;
+    if (*pos < *n && indices[*pos] == sstable_index) {
+        dbeel_set_last_error("lsm reader: sstable already in the reader");
         return DBEEL_ERR_INVALID_ARG;
     }
+    return DBEEL_OK;
+}
+
+void note_new_run(uint64_t* indices, size_t* n, size_t pos,
+                  uint64_t sstable_index) {
+    for (size_t i = *n; i > pos; i--) indices[i] = indices[i - 1];
+    indices[pos] = sstable_index;
+    *n += 1;
+}
+} // namespace
+
+extern "C" int dbeel_lsm_reader_add(const char* dir_c, dbeel_gpu_reader* rd,
+                                    uint64_t* indices, size_t* n,
+                                    uint64_t sstable_index) {
+    size_t pos = 0;
+    int prc = new_run_position(dir_c, rd, indices, n, sstable_index, &pos);
+    if (prc != DBEEL_OK) return prc;
     std::string dir(dir_c);
     std::vector<uint8_t> data, index, bloom;
     if (!read_whole(file_path(dir, sstable_index, "data"), data) ||
@@ -571,9 +591,43 @@ extern "C" int dbeel_lsm_reader_add(const char* dir_c, dbeel_gpu_reader* rd,
     }
     int rc = dbeel_gpu_reader_insert_run(rd, pos, &view, &bview);
     if (rc != DBEEL_OK) return rc;
-    for (size_t i = *n; i > pos; i--) indices[i] = indices[i - 1];
-    indices[pos] = sstable_index;
-    *n += 1;
+    note_new_run(indices, n, pos, sstable_index);
+    return DBEEL_OK;
+}
+
+extern "C" int dbeel_lsm_reader_flush(
+    const char* dir_c, dbeel_gpu_reader* rd, uint64_t* indices, size_t* n,
+    uint64_t sstable_index, uint64_t n_writes, const uint8_t* keys,
+    const uint64_t* key_offsets, const uint8_t* values,
+    const uint64_t* value_offsets, const uint8_t* timestamps) {
+    size_t pos = 0;
+    int rc = new_run_position(dir_c, rd, indices, n, sstable_index, &pos);
+    if (rc != DBEEL_OK) return rc;
+    std::string dp = file_path(dir_c, sstable_index, "data");
+    std::string ip = file_path(dir_c, sstable_index, "index");
+    if (exists(dp) || exists(ip)) {
+        dbeel_set_last_error("lsm_reader_flush: sstable files already exist");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    dbeel_compact_result res{};
+    rc = dbeel_gpu_reader_write_batch(rd, pos, n_writes, keys, key_offsets,
+                                      values, value_offsets, timestamps,
+                                      /*build_bloom=*/0, &res, nullptr,
+                                      nullptr, nullptr);
+    /* an empty memtable flushes nothing (lsm_tree.rs:850-852) */
+    if (rc != DBEEL_OK || n_writes == 0) return rc;
+    bool ok = write_whole(dp, res.data, res.data_len) &&
+              write_whole(ip, res.index, res.index_len);
+    dbeel_gpu_result_free(&res);
+    if (!ok) {
+        unlink(dp.c_str());
+        unlink(ip.c_str());
+        (void)dbeel_reader_drop_run(rd, pos);
+        dbeel_set_last_error("lsm_reader_flush: cannot write the sstable's "
+                             "data/index file");
+        return DBEEL_ERR_IO;
+    }
+    note_new_run(indices, n, pos, sstable_index);
     return DBEEL_OK;
 }
 

@@ -442,6 +442,51 @@ class ReaderCompactStats(ctypes.Structure):
         return d
 
 
+class WriteBatchStats(ctypes.Structure):
+    """dbeel_write_batch_stats."""
+    _fields_ = [
+        ("h2d_ms", ctypes.c_double),
+        ("order_ms", ctypes.c_double),
+        ("encode_ms", ctypes.c_double),
+        ("adopt_ms", ctypes.c_double),
+        ("d2h_ms", ctypes.c_double),
+        ("writes_in", ctypes.c_uint64),
+        ("entries_out", ctypes.c_uint64),
+        ("data_bytes_out", ctypes.c_uint64),
+        ("prefix_tied", ctypes.c_uint64),
+        ("d2h_bytes", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+_U8P = ctypes.POINTER(ctypes.c_uint8)
+_U64P = ctypes.POINTER(ctypes.c_uint64)
+_BATCH_ARGTYPES = [ctypes.c_uint64, _U8P, _U64P, _U8P, _U64P, _U8P]
+
+
+def _write_arrays(writes):
+    """A write batch — an iterable of (key, value, timestamp) in arrival
+    order, unsorted, keys may repeat, b"" = tombstone — as the C ABI's
+    arrays: (n, [five ctypes pointers], keepalive)."""
+    writes = list(writes)
+    n = len(writes)
+    ka = np.frombuffer(b"".join(w[0] for w in writes) or b"\0", dtype=np.uint8)
+    va = np.frombuffer(b"".join(w[1] for w in writes) or b"\0", dtype=np.uint8)
+    koff = np.zeros(n + 1, dtype=np.uint64)
+    voff = np.zeros(n + 1, dtype=np.uint64)
+    koff[1:] = np.cumsum(np.array([len(w[0]) for w in writes], dtype=np.uint64))
+    voff[1:] = np.cumsum(np.array([len(w[1]) for w in writes], dtype=np.uint64))
+    ts = np.frombuffer(
+        b"".join(int(w[2]).to_bytes(16, "little", signed=True)
+                 for w in writes) or b"\0", dtype=np.uint8)
+    ptrs = [ka.ctypes.data_as(_U8P), koff.ctypes.data_as(_U64P),
+            va.ctypes.data_as(_U8P), voff.ctypes.data_as(_U64P),
+            ts.ctypes.data_as(_U8P)]
+    return n, ptrs, (ka, va, koff, voff, ts)
+
+
 def _load_reader() -> ctypes.CDLL:
     lib = load()
     if not hasattr(lib, "_reader_ready"):
@@ -502,6 +547,15 @@ def _load_reader() -> ctypes.CDLL:
         ]
         lib.dbeel_gpu_reader_scan_end.restype = None
         lib.dbeel_gpu_reader_scan_end.argtypes = [ctypes.c_void_p]
+        lib.dbeel_gpu_reader_write_batch.restype = ctypes.c_int
+        lib.dbeel_gpu_reader_write_batch.argtypes = (
+            [ctypes.c_void_p, ctypes.c_size_t] + _BATCH_ARGTYPES + [
+                ctypes.c_int, ctypes.POINTER(CompactResult),
+                ctypes.POINTER(_U8P), _U64P,
+                ctypes.POINTER(WriteBatchStats)])
+        lib.dbeel_gpu_flush_batch.restype = ctypes.c_int
+        lib.dbeel_gpu_flush_batch.argtypes = _BATCH_ARGTYPES + [
+            ctypes.c_int, ctypes.POINTER(CompactResult)]
         lib._reader_ready = True
     return lib
 
@@ -675,6 +729,47 @@ class Reader:
         self._check(self._lib.dbeel_gpu_reader_insert_run(
             self._h, pos, views, None if bview is None else ctypes.byref(bview)))
         del keepalive
+
+    def write_batch(self, writes, pos: int | None = None,
+                    build_bloom: bool = False, fetch: bool = True):
+        """The memtable and its flush in one call: `writes` is an iterable
+        of (key, value, timestamp) in ARRIVAL order — unsorted, keys may
+        repeat, b"" is a tombstone. The batch is sorted, the last write of
+        every key kept (whatever the timestamps), and the run encoded on
+        the device straight into a new table at position pos (None = the
+        end: gets see it first). Returns (data, index, bloom_bytes, stats):
+        the run's file bytes (None, None when fetch=False), its "DBLM"
+        filter bytes (None unless build_bloom and fetch) and the stats
+        dict. An empty batch changes nothing. On failure the reader is
+        unchanged."""
+        if not self._h:
+            raise ValueError("reader is closed")
+        n, ptrs, keepalive = _write_arrays(writes)
+        res = CompactResult()
+        st = WriteBatchStats()
+        bp = _U8P()
+        bn = ctypes.c_uint64()
+        want_bloom = bool(build_bloom) and fetch
+        rc = self._lib.dbeel_gpu_reader_write_batch(
+            self._h, self.n_runs if pos is None else pos, n, *ptrs,
+            int(build_bloom), ctypes.byref(res) if fetch else None,
+            ctypes.byref(bp) if want_bloom else None,
+            ctypes.byref(bn) if want_bloom else None, ctypes.byref(st))
+        del keepalive
+        self._check(rc)
+        data = index = bloom_bytes = None
+        try:
+            if fetch:
+                data = _ptr_bytes(res.data, res.data_len)
+                index = _ptr_bytes(res.index, res.index_len)
+            if want_bloom and bp:
+                bloom_bytes = _ptr_bytes(bp, int(bn.value))
+        finally:
+            if fetch:
+                self._lib.dbeel_gpu_result_free(ctypes.byref(res))
+            if want_bloom:
+                self._lib.dbeel_gpu_bloom_free(bp)
+        return data, index, bloom_bytes, st.as_dict()
 
     def compact_begin(self, positions, keep_tombstones: bool,
                       bloom: bool = False, fetch: bool = True):
@@ -913,6 +1008,27 @@ def encode_run(entries, device: int = 0):
     finally:
         lib.dbeel_gpu_result_free(ctypes.byref(res))
     return data, index, n
+
+
+def flush_batch(writes, device: int = 0):
+    """Reader.write_batch's run with no reader: writes = iterable of (key,
+    value, timestamp) in arrival order, unsorted, keys may repeat. Returns
+    (data_bytes, index_bytes, n) — what encode_run gives for the batch
+    sorted by key with the last write of every key kept."""
+    lib = _load_reader()
+    n, ptrs, keepalive = _write_arrays(writes)
+    res = CompactResult()
+    rc = lib.dbeel_gpu_flush_batch(n, *ptrs, device, ctypes.byref(res))
+    del keepalive
+    if rc != 0:
+        raise DbeelGpuError(rc, lib.dbeel_gpu_last_error().decode())
+    try:
+        data = _ptr_bytes(res.data, res.data_len)
+        index = _ptr_bytes(res.index, res.index_len)
+        n_out = int(res.entries_written)
+    finally:
+        lib.dbeel_gpu_result_free(ctypes.byref(res))
+    return data, index, n_out
 
 
 class Job:

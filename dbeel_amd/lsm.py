@@ -178,6 +178,33 @@ def reader_add(dir: str, reader, indices, sstable_index: int):
     return [int(idx[i]) for i in range(n.value)]
 
 
+def reader_flush(dir: str, reader, indices, sstable_index: int, writes):
+    """The flush itself: `writes` — an iterable of (key, value, timestamp)
+    in arrival order, unsorted, keys may repeat — is sorted, deduplicated
+    (last write wins) and encoded on the device into a new table of the
+    open reader at sstable_index's ascending-index position, and written
+    as {sstable_index:020}.data/.index (no .bloom). Returns the new
+    indices list; the reader then answers as a fresh open_reader(dir)
+    would. An empty batch writes nothing."""
+    from .engine import _BATCH_ARGTYPES, _write_arrays
+
+    lib = load()
+    if not hasattr(lib, "_lsm_flush_ready"):
+        lib.dbeel_lsm_reader_flush.restype = ctypes.c_int
+        lib.dbeel_lsm_reader_flush.argtypes = [
+            ctypes.c_char_p, ctypes.c_void_p,
+            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_size_t),
+            ctypes.c_uint64] + _BATCH_ARGTYPES
+        lib._lsm_flush_ready = True
+    idx, n = _indices_array(indices)
+    nw, ptrs, keepalive = _write_arrays(writes)
+    rc = lib.dbeel_lsm_reader_flush(dir.encode(), reader._h, idx,
+                                    ctypes.byref(n), sstable_index, nw, *ptrs)
+    del keepalive
+    _check(rc, lib)
+    return [int(idx[i]) for i in range(n.value)]
+
+
 def reader_compact(dir: str, reader, indices, compact_indices,
                    output_index: int, keep_tombstones: bool,
                    device_unused=None,

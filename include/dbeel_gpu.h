@@ -319,8 +319,8 @@ void dbeel_gpu_reader_compact_abort(dbeel_gpu_reader* reader);
  * or index, data_cap == 0 or index_cap < 16 is DBEEL_ERR_INVALID_ARG.
  *
  * Liveness: a scan sees the list as dbeel_gpu_reader_get does (a pending
- * compaction is invisible). insert_run and compact_commit change the list
- * and invalidate every open scan: next then returns DBEEL_ERR_INVALID_ARG
+ * compaction is invisible). insert_run, a non-empty write_batch and
+ * compact_commit change the list and invalidate every open scan: next then returns DBEEL_ERR_INVALID_ARG
  * ("stale scan") and the caller restarts; compact_begin / compact_abort do
  * not. (Divergence: the reference's iterator keeps its cloned list alive,
  * lsm_tree.rs:175-177.) Any number of scans may be open on a reader, under
@@ -368,6 +368,77 @@ int dbeel_gpu_encode_run(uint64_t n_entries, const uint8_t* keys,
                          const uint64_t* value_offsets,
                          const uint8_t* timestamps, int device,
                          dbeel_compact_result* out);
+
+/* ---- Write batch (the memtable and its flush, on the device) ----
+ * The reference's memtable is a RedBlackTree<Vec<u8>, EntryValue> whose set
+ * replaces the value of an equal key WHATEVER the timestamps are
+ * (rbtree_arena/src/lib.rs:497-511); flush iterates it in key order into
+ * EntryWriter (lsm_tree.rs:882-889, 925-946) and pushes the table onto the
+ * end of the sstable list with no bloom (lsm_tree.rs:901-915); an empty
+ * memtable flushes nothing (lsm_tree.rs:850-852).
+ *
+ * Input: n_writes writes in ARRIVAL order (array order), unsorted, keys may
+ * repeat — the arrays of dbeel_gpu_encode_run; an empty value is a
+ * tombstone. Output run: one entry per distinct key, keys ascending in
+ * byte-lexicographic order (a proper prefix first, the empty key legal),
+ * each with the value and timestamp of its LAST arrival, even when an
+ * earlier arrival has a larger timestamp; tombstones are kept. The bytes
+ * are what dbeel_gpu_encode_run returns for that sorted, deduplicated
+ * stream.
+ *
+ * reader_write_batch sorts, deduplicates and encodes the batch straight
+ * into a new right-sized resident table and inserts it at pos in
+ * [0, n_runs] exactly as dbeel_gpu_reader_insert_run would (pos == n_runs
+ * is the reference's push: gets see it first; open scans go stale; a
+ * pending compaction's positions shift). out (NULL = leave the bytes on the
+ * device) receives the run for the caller to persist; with build_bloom the
+ * table gets a filter with dbeel_gpu_job_bloom's parameters, and
+ * bloom_bytes / bloom_len (both NULL, or both set; free with
+ * dbeel_gpu_bloom_free) its "DBLM" file — the bytes compact_begin({pos},
+ * keep_tombstones = 1, build_bloom = 1) returns for the table afterwards.
+ * All device work runs on the reader's stream; uploads are true async DMA
+ * when the arrays are registered with dbeel_gpu_pin_host. Staging and sort
+ * scratch belong to the call.
+ *
+ * Validated on the host before any device call, in this order: NULL reader,
+ * or a NULL array with n_writes != 0; pos > n_runs; a mismatched bloom
+ * pair; n_writes >= 2^31; a descending offset; a reader at 64 runs with
+ * n_writes != 0 (all DBEEL_ERR_INVALID_ARG); a write with
+ * 32 + klen + vlen > u32::MAX (DBEEL_ERR_ITEM_TOO_LARGE). n_writes == 0 is
+ * a successful no-op: no table, no generation change, zeroed outputs. On
+ * any failure the reader answers as before and holds the same table_bytes.
+ *
+ * The order stage has two paths with the same result, chosen by
+ * DBEEL_BATCH_ORDER in the environment, read on every call: "merge" (the
+ * default: it measured faster on most shapes) is one merge
+ * sort over all writes by (8-byte key prefix, key, arrival); "radix" is a
+ * stable radix sort on (prefix, arrival) followed by a merge sort of only
+ * the writes whose prefix equals another's (stats.prefix_tied counts them
+ * on both paths).
+ *
+ * flush_batch is the same pipeline with no reader: bytes only. */
+typedef struct {
+    double   h2d_ms, order_ms, encode_ms, adopt_ms, d2h_ms; /* HIP events on
+                 the reader's stream: upload | prefixes + order | survivor
+                 flags, scans, table allocation, encode | k_reader_adopt |
+                 fetch of out / filter bytes, 0 when not asked */
+    uint64_t writes_in, entries_out, data_bytes_out;
+    uint64_t prefix_tied;  /* writes whose 8-byte prefix equals another write's */
+    uint64_t d2h_bytes;
+} dbeel_write_batch_stats;
+
+int dbeel_gpu_reader_write_batch(dbeel_gpu_reader* reader, size_t pos,
+        uint64_t n_writes, const uint8_t* keys, const uint64_t* key_offsets,
+        const uint8_t* values, const uint64_t* value_offsets,
+        const uint8_t* timestamps, int build_bloom,
+        dbeel_compact_result* out /* NULL = leave on device */,
+        uint8_t** bloom_bytes, uint64_t* bloom_len /* both or neither */,
+        dbeel_write_batch_stats* stats /* may be NULL */);
+
+int dbeel_gpu_flush_batch(uint64_t n_writes, const uint8_t* keys,
+        const uint64_t* key_offsets, const uint8_t* values,
+        const uint64_t* value_offsets, const uint8_t* timestamps,
+        int device, dbeel_compact_result* out);
 
 /* ---- Resident-job API (benchmarking / repeated compactions) ----
  * Uploads the runs to `device` once; each run executes the device pipeline

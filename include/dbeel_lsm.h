@@ -115,10 +115,29 @@ int dbeel_lsm_reader_open(const char* dir, int device,
  * answering from the old list. With DBEEL_LSM_CRASH_AFTER_JOURNAL set it
  * stops after the journal as dbeel_lsm_compact does (reader and indices
  * unchanged): the directory then needs dbeel_lsm_replay and the reader a
- * reopen. */
+ * reopen.
+ *
+ * reader_flush: the flush itself (lsm_tree.rs:850-915) instead of
+ * reader_add after a host-side flush. The write batch (the arrays of
+ * dbeel_gpu_reader_write_batch, arrival order) is sorted, deduplicated and
+ * encoded on the device into a new table at sstable_index's
+ * ascending-index position, and the run is written as
+ * {sstable_index:020}.data / .index under their final names — no .bloom:
+ * the reference's flush passes None. An index already present is
+ * DBEEL_ERR_INVALID_ARG before anything is written; a file that cannot be
+ * written is DBEEL_ERR_IO, with the table taken out of the reader again and
+ * what was written removed. n_writes == 0 writes nothing and changes
+ * nothing. */
 int dbeel_lsm_reader_add(const char* dir, struct dbeel_gpu_reader* reader,
                          uint64_t* indices, size_t* n,
                          uint64_t sstable_index);
+int dbeel_lsm_reader_flush(const char* dir, struct dbeel_gpu_reader* reader,
+                           uint64_t* indices, size_t* n,
+                           uint64_t sstable_index, uint64_t n_writes,
+                           const uint8_t* keys, const uint64_t* key_offsets,
+                           const uint8_t* values,
+                           const uint64_t* value_offsets,
+                           const uint8_t* timestamps);
 int dbeel_lsm_reader_compact(const char* dir, struct dbeel_gpu_reader* reader,
                              uint64_t* indices, size_t* n,
                              const uint64_t* compact_indices, size_t n_compact,

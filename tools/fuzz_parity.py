@@ -204,9 +204,45 @@ def paged_scan_step(rng, rd, runs, stored):
     return None
 
 
+def write_batch_step(rng, rd, runs, blooms, queries):
+    """One random write batch (arrival order, repeated keys drawn from the
+    query set, tombstones, any timestamp; either order path) into the open
+    reader at a random position, against the memtable model; runs and
+    blooms are edited in place to the list the reader should now hold."""
+    sys.path.insert(0, os.path.join(
+        os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import batch_model
+
+    pool = queries or [b"", b"k"]
+    writes = []
+    for _ in range(int(rng.integers(0, 400))):
+        k = pool[int(rng.integers(0, len(pool)))]
+        v = (b"" if rng.random() < 0.2 else bytes(rng.integers(
+            0, 256, int(rng.integers(0, 80)), dtype=np.uint8)))
+        writes.append((k, v, int(rng.integers(-2**62, 2**62))))
+    pos = int(rng.integers(0, len(runs) + 1))
+    with_bloom = bool(rng.integers(0, 2))
+    order = ("radix", "merge")[int(rng.integers(0, 2))]
+    os.environ["DBEEL_BATCH_ORDER"] = order
+    try:
+        gd, gi, gb, st = rd.write_batch(writes, pos=pos,
+                                        build_bloom=with_bloom)
+    finally:
+        os.environ.pop("DBEEL_BATCH_ORDER", None)
+    what = f"write batch of {len(writes)} at {pos} order={order}"
+    if (gd, gi) != batch_model.flush_run(writes):
+        return f"{what}: run differs from the memtable model"
+    if st["prefix_tied"] != batch_model.prefix_tied(writes):
+        return f"{what}: prefix_tied {st['prefix_tied']}"
+    if writes:
+        runs.insert(pos, (gd, gi))
+        blooms.insert(pos, gb)
+    return None
+
+
 def live_reader_step(rng, rd, runs, blooms, queries, device):
-    """One random insert and one random compaction applied to the open
-    reader, each compared field for field against a freshly opened reader
+    """One random insert, one random write batch and one random compaction
+    applied to the open reader, each compared field for field against a freshly opened reader
     over the resulting list (the compaction's output from the oracle)."""
     from dbeel_amd.engine import Reader
 
@@ -229,6 +265,13 @@ def live_reader_step(rng, rd, runs, blooms, queries, device):
         runs.insert(pos, new)
         blooms.insert(pos, None)
         why = differs(f"insert at {pos}")
+        if why:
+            return why
+    if len(runs) < 64:
+        why = write_batch_step(rng, rd, runs, blooms, queries)
+        if why:
+            return why
+        why = differs("write batch")
         if why:
             return why
     n = len(runs)

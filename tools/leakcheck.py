@@ -3,8 +3,9 @@
 streamed ingests (each creates ~per-chunk HIP events), batched jobs,
 scans, sliced compactions and resident readers (open / get x N / paged
 scans begin + next + end, one left for close to end / insert / compact
-begin + abort + commit / close), reporting hipMemGetInfo drift. A leak in
-any path shows as monotonically shrinking free memory.
+begin + abort + commit / write batches with fetch on and off, a filter,
+both order paths and a refused call / close), reporting hipMemGetInfo
+drift. A leak in any path shows as monotonically shrinking free memory.
 
     python tools/leakcheck.py --iters 40
 """
@@ -20,9 +21,11 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import dbeel_amd  # noqa: E402
 from dbeel_amd.engine import (  # noqa: E402
     BatchJob,
+    DbeelGpuError,
     Job,
     Reader,
     compact_sliced,
+    flush_batch,
     load,
     pin_host,
     scan,
@@ -63,6 +66,12 @@ def main():
     for d, i in runs:  # half present, half absent
         recs = np.frombuffer(i, dtype="<u8").reshape(-1, 2)[:2500, 0]
         probe_keys += [d[int(o) + 8 : int(o) + 24].tobytes() for o in recs]
+
+    # an unsorted write batch with repeated keys, shared 8-byte prefixes
+    # among them (the settle stage allocates only then)
+    batch = [(k if j % 3 else b"user:000" + k[:5],
+              bytes(probe_rng.integers(0, 256, j % 97, dtype=np.uint8)), j)
+             for j, k in enumerate(probe_keys + probe_keys[:5000])]
 
     os.environ["DBEEL_STREAM_CHUNK_MB"] = "1"
     base = None
@@ -113,7 +122,20 @@ def main():
                 rd.compact_abort()
                 rd.compact([1, 3, 4], 0, False, bloom=True)
                 rd.compact_begin([0, 1], True, fetch=False)  # close aborts
+                # write batches: staging, sort scratch and pinned record
+                # are the call's; the tables go with close
+                for fetch, bloom in ((True, True), (False, False)):
+                    rd.write_batch(batch, build_bloom=bloom, fetch=fetch)
+                os.environ["DBEEL_BATCH_ORDER"] = "radix"
+                rd.write_batch(batch[::3], pos=0)
+                del os.environ["DBEEL_BATCH_ORDER"]
+                try:
+                    rd.write_batch(batch, pos=99)  # fails before the device
+                    raise SystemExit("write_batch accepted a bad position")
+                except DbeelGpuError:
+                    pass
                 rd.get(probe_keys[:4000])
+            flush_batch(batch[:7000], device=0)
             f = free_mem()
             if base is None:
                 base = f
