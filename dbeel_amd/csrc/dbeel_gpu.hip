@@ -2642,7 +2642,9 @@ extern "C" int dbeel_gpu_lookup(const dbeel_run_view* runs, size_t n_runs,
 /*                      prefix slice (8 keys per 64-B line, top       */
 /*                      levels cache-resident), then the equal-prefix */
 /*                      range is resolved by binary search with full  */
-/*                      key compares on the blob.                     */
+/*                      key compares on the blob. A non-empty         */
+/*                      memtable is searched the same way ahead of    */
+/*                      the tables, in an instantiation of its own.   */
 /*   rocPRIM scan     : value_len -> exclusive value offsets.         */
 /*   k_reader_gather  : wave per hit, 8-B chunks, exact-length reads. */
 /*   k_reader_adopt   : a compaction output copied device-to-device   */
@@ -2665,7 +2667,21 @@ struct ReaderBloom {
 struct ReaderPfx {
     const uint64_t* p[MAX_RUNS];
 };
-static_assert(sizeof(RunsDesc) + sizeof(ReaderPfx) + 64 <= 4096,
+/* The memtable as the search and gather kernels see it: one sorted run
+ * with unique keys that the engine wrote itself (so its records are read
+ * without the bounds checks of load_entry). count == 0 = empty: the search
+ * then runs as the instantiation without the leg, and no hit names it for
+ * the gather. It is not in RunsDesc — with 64
+ * tables its position, n_runs, lies past the descriptor's arrays. */
+struct ReaderMem {
+    const uint8_t* data;
+    const uint8_t* index;
+    const uint64_t* pfx;
+    uint64_t count;
+};
+static_assert(sizeof(ReaderMem) == 32, "memtable leg: 32 B of arguments");
+static_assert(sizeof(RunsDesc) + sizeof(ReaderPfx) + sizeof(ReaderMem) + 64 <=
+                  4096,
               "k_reader_search arguments must fit the kernarg segment");
 
 /* stats slots of dbeel_get_stats, in order */
@@ -2697,8 +2713,45 @@ __global__ void k_reader_prepare(RunsDesc R, uint64_t* pfx, uint32_t* err) {
     }
 }
 
+/* The memtable leg of the search: the table loop's shape — bisect the
+ * prefixes, then settle the equal-prefix stretch by bisection with full key
+ * compares — over a run the engine wrote (its records are read without
+ * load_entry's bounds checks). On a match off / vlen receive the value's
+ * offset in the memtable's data and its length. */
+__device__ __forceinline__ bool mem_search(const ReaderMem& M,
+                                           const uint8_t* key, uint64_t klen,
+                                           uint64_t qp, uint64_t& off,
+                                           uint64_t& vlen) {
+    uint64_t lo = pfx_lower_bound(M.pfx, M.count, qp);
+    if (lo >= M.count || M.pfx[lo] != qp) return false;
+    uint64_t end = lo + 1;
+    if (end < M.count && M.pfx[end] == qp)
+        end = pfx_upper_bound(M.pfx, end + 1, M.count, qp);
+    while (lo < end) {
+        const uint64_t mid = (lo + end) >> 1;
+        const uint8_t* rec = M.index + mid * 16;
+        const uint64_t eoff = ld_u64(rec);
+        const uint64_t mklen = ld_u32(rec + 8) - 8;
+        const int cmp = cmp_keys(M.data + eoff + 8, mklen, key, klen);
+        if (cmp == 0) {
+            off = eoff + 16 + mklen;
+            vlen = (uint64_t)ld_u32(rec + 12) - 32 - mklen;
+            return true;
+        }
+        if (cmp < 0)
+            lo = mid + 1;
+        else
+            end = mid;
+    }
+    return false;
+}
+
+/* MEM = the memtable is not empty. With an empty one the launch takes the
+ * <false> instantiation, whose code is the search without a memtable: the
+ * get path does not pay for the feature until it is used. */
+template <bool MEM>
 __global__ __launch_bounds__(READER_BLOCK) void k_reader_search(
-    RunsDesc R, ReaderPfx pfx, const ReaderBloom* blooms,
+    RunsDesc R, ReaderPfx pfx, ReaderMem mem, const ReaderBloom* blooms,
     const uint8_t* keys, const uint64_t* key_off, uint64_t n_keys,
     dbeel_lookup_hit* out, unsigned long long* stats) {
     __shared__ unsigned long long s_stats[RS_N];
@@ -2718,7 +2771,19 @@ __global__ __launch_bounds__(READER_BLOCK) void k_reader_search(
         uint64_t hseed = 0, h1 = 0, h2 = 0;
         int best_run = -1;
         uint64_t best_off = 0, best_vlen = 0;
-        for (int r = R.n_runs - 1; r >= 0; r--) {
+        int r = R.n_runs - 1;
+        /* a non-empty memtable is consulted before every table
+         * (lsm_tree.rs:676-685) and counts as one visit to an unfiltered
+         * run; a key found there is reported at the position a flush will
+         * give it */
+        if constexpr (MEM) {
+            c[RS_SEARCHES]++;
+            if (mem_search(mem, key, klen, qp, best_off, best_vlen)) {
+                best_run = R.n_runs;
+                r = -1;
+            }
+        }
+        for (; r >= 0; r--) {
             const ReaderBloom B = blooms[r];
             if (B.bits) {
                 c[RS_PROBES]++;
@@ -2809,7 +2874,8 @@ struct HitValueLen {
 /* One wave per query moves its value in 8-B chunks (byte tail by lane 0),
  * reading exactly value_len bytes — k_copy's staged span assumes >= 32-B
  * segments and cannot take 0/1-byte values. */
-__global__ void k_reader_gather(RunsDesc R, const dbeel_lookup_hit* hits,
+__global__ void k_reader_gather(RunsDesc R, const uint8_t* mem_data,
+                                const dbeel_lookup_hit* hits,
                                 const uint64_t* val_off, uint64_t n_keys,
                                 uint8_t* values) {
     uint32_t lane = threadIdx.x & 63;
@@ -2818,7 +2884,10 @@ __global__ void k_reader_gather(RunsDesc R, const dbeel_lookup_hit* hits,
     for (uint64_t q = wave; q < n_keys; q += n_waves) {
         const dbeel_lookup_hit h = hits[q];
         if (h.run < 0 || h.value_len == 0) continue;
-        wave_copy_bytes(values + val_off[q], R.data[h.run] + h.value_offset,
+        /* run == n_runs names the memtable; with 64 tables that index lies
+         * past R's arrays, so it is resolved before any of them is read */
+        const uint8_t* src = h.run >= R.n_runs ? mem_data : R.data[h.run];
+        wave_copy_bytes(values + val_off[q], src + h.value_offset,
                         h.value_len, lane);
     }
 }
@@ -2851,6 +2920,35 @@ struct ScanPageTotals {
 
 struct dbeel_gpu_reader_scan;
 
+/* The resident memtable: one sorted run with unique keys in the table
+ * layout (16 B pad | data | index | 16 B pad, plus the dense prefix array),
+ * held in buf[cur]. A put builds its successor in buf[cur ^ 1] and swaps on
+ * success, so a failed put leaves it untouched. The pair grows
+ * geometrically and is kept across flush and clear; none of it counts in
+ * table_bytes. */
+struct ReaderMemtable {
+    struct Buf {
+        uint8_t* d_run = nullptr;
+        uint64_t run_cap = 0; /* bytes */
+        uint64_t* d_pfx = nullptr;
+        uint64_t pfx_cap = 0; /* bytes */
+    } buf[2];
+    int cur = 0;
+    uint64_t count = 0, data_len = 0, puts = 0;
+
+    const uint8_t* data() const { return buf[cur].d_run + 16; }
+    const uint8_t* index() const { return data() + data_len; }
+    uint64_t reserved() const {
+        return buf[0].run_cap + buf[0].pfx_cap + buf[1].run_cap +
+               buf[1].pfx_cap;
+    }
+    ReaderMem view() const {
+        if (!count) return ReaderMem{nullptr, nullptr, nullptr, 0};
+        return ReaderMem{data(), index(), buf[cur].d_pfx, count};
+    }
+    void drop() { count = data_len = puts = 0; }
+};
+
 struct dbeel_gpu_reader {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -2866,6 +2964,9 @@ struct dbeel_gpu_reader {
     bool has_pending = false;
     ReaderTable pending;
     std::vector<uint32_t> pending_pos; /* its input tables, ascending    */
+    /* puts not flushed yet; gets consult it before every table, scans do
+     * not see it */
+    ReaderMemtable mem;
     /* per-batch scratch, grown on demand and reused */
     uint8_t* d_keys = nullptr;
     uint64_t keys_cap = 0;
@@ -2997,6 +3098,10 @@ extern "C" void dbeel_gpu_reader_close(dbeel_gpu_reader* rd) {
     dbeel_gpu_reader_compact_abort(rd);
     reader_end_scans(rd);
     for (ReaderTable& t : rd->tables) table_free(t);
+    for (ReaderMemtable::Buf& b : rd->mem.buf) {
+        (void)hipFree(b.d_run);
+        (void)hipFree(b.d_pfx);
+    }
     (void)hipFree(rd->d_blooms);
     (void)hipFree(rd->d_keys);
     (void)hipFree(rd->d_batch);
@@ -4154,6 +4259,403 @@ extern "C" __attribute__((visibility("hidden"))) int dbeel_reader_drop_run(
     return DBEEL_OK;
 }
 
+/* ------------------------------------------------------------------ */
+/* Resident memtable (include/dbeel_gpu.h): puts visible to gets,     */
+/* flushed as one run                                                 */
+/*                                                                    */
+/* A put orders its batch with the write-batch stages (batch_order,   */
+/* batch_encode) into a temporary run B, then merges B into the       */
+/* memtable M, B winning equal keys — the rbtree's set() across       */
+/* batches (rbtree_arena/src/lib.rs:497-511):                         */
+/*   k_mem_rank : thread per entry of M and of B. Each bisects the    */
+/*                OTHER run (prefix array, then the equal-prefix      */
+/*                stretch with full key compares — never a walk) for  */
+/*                its lower bound, which added to its own index is    */
+/*                its slot in the merged order; an M entry whose key  */
+/*                B holds is written without the keep flag. The slots */
+/*                are a permutation of [0, m + b).                    */
+/*   survivor_scans, k_emit, k_winmap, k_copy : the compaction's own  */
+/*                tail over the two-run descriptor {M, B}, verbatim   */
+/*                entry copy into the spare buffer.                   */
+/*   k_reader_adopt : the merged prefix array.                        */
+/* ------------------------------------------------------------------ */
+
+struct MemPfx {
+    const uint64_t* p[2];
+};
+
+/* Lower bound of (key, klen) in run r of R, whose n entries have the
+ * prefixes P; eq = whether the entry there has that very key. */
+__device__ __forceinline__ uint64_t mem_lower_bound(const RunsDesc& R, int r,
+                                                    const uint64_t* P,
+                                                    uint64_t qp,
+                                                    const uint8_t* key,
+                                                    uint64_t klen, bool& eq) {
+    const uint64_t n = R.count[r];
+    const uint64_t lo = pfx_lower_bound(P, n, qp);
+    const uint64_t end = pfx_upper_bound(P, lo, n, qp);
+    const uint64_t lb = blob_lower_bound(R, r, lo, end, key, klen);
+    eq = false;
+    EView m;
+    if (lb < end && load_entry(R, r, lb, m))
+        eq = cmp_keys(m.key, m.klen, key, klen) == 0;
+    return lb;
+}
+
+/* R = {M, B}. Every slot is below R.total whatever the input holds (a
+ * lower bound never exceeds the other run's count), so the store is in
+ * bounds by construction; rrec is zeroed beforehand, so a slot nobody
+ * claimed keeps nothing. */
+__global__ void k_mem_rank(RunsDesc R, MemPfx pfx, RankRec* rrec,
+                           uint32_t* err) {
+    const uint64_t m = R.count[0];
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         g < R.total; g += stride) {
+        const int r = g < m ? 0 : 1;
+        const uint64_t i = r ? g - m : g;
+        EView e;
+        if (!load_entry(R, r, i, e)) { /* the engine wrote both runs */
+            atomicOr(err, DERR_CORRUPT);
+            continue;
+        }
+        bool eq;
+        const uint64_t lb = mem_lower_bound(R, r ^ 1, pfx.p[r ^ 1], pfx.p[r][i],
+                                            e.key, e.klen, eq);
+        /* an equal pair: M's entry takes the lower slot and is dropped */
+        const uint64_t slot = i + lb + ((r && eq) ? 1 : 0);
+        const bool keep = r || !eq;
+        RankRec rec;
+        rec.src = ((uint64_t)r << 48) | e.off | (keep ? RR_KEEP : 0);
+        rec.key_size = e.key_size;
+        rec.full_size = e.full_size;
+        rrec[slot] = rec;
+    }
+}
+
+/* Makes buf hold a run of run_bytes and n prefixes; grows geometrically.
+ * The buffer's old contents are not kept: it is the spare. */
+static hipError_t mem_reserve(ReaderMemtable::Buf& buf, uint64_t run_bytes,
+                              uint64_t n) {
+    if (run_bytes > buf.run_cap) {
+        const uint64_t want =
+            run_bytes > 2 * buf.run_cap ? run_bytes : 2 * buf.run_cap;
+        (void)hipFree(buf.d_run);
+        buf.d_run = nullptr;
+        buf.run_cap = 0;
+        hipError_t e = hipMalloc(&buf.d_run, want);
+        if (e != hipSuccess) return e;
+        buf.run_cap = want;
+    }
+    const uint64_t pfx_bytes = (n ? n : 1) * sizeof(uint64_t);
+    if (pfx_bytes > buf.pfx_cap) {
+        const uint64_t want =
+            pfx_bytes > 2 * buf.pfx_cap ? pfx_bytes : 2 * buf.pfx_cap;
+        (void)hipFree(buf.d_pfx);
+        buf.d_pfx = nullptr;
+        buf.pfx_cap = 0;
+        hipError_t e = hipMalloc(&buf.d_pfx, want);
+        if (e != hipSuccess) return e;
+        buf.pfx_cap = want;
+    }
+    return hipSuccess;
+}
+
+static inline uint64_t mem_run_bytes(uint64_t data_len, uint64_t count) {
+    return data_len + count * 16 + 32;
+}
+
+extern "C" int dbeel_gpu_reader_put(dbeel_gpu_reader* rd, uint64_t n_writes,
+                                    const uint8_t* keys,
+                                    const uint64_t* key_offsets,
+                                    const uint8_t* values,
+                                    const uint64_t* value_offsets,
+                                    const uint8_t* timestamps,
+                                    dbeel_memtable_put_stats* stats) {
+    g_err[0] = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (!rd) {
+        set_err("reader_put: null reader");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    const BatchIn in = {n_writes, keys, key_offsets, values, value_offsets,
+                        timestamps};
+    int rc = batch_check_arrays("reader_put", in);
+    if (rc) return rc;
+    uint64_t too_large = 0;
+    rc = batch_check_offsets("reader_put", in, &too_large);
+    if (rc) return rc;
+    ReaderMemtable& M = rd->mem;
+    if (M.count + in.n >= (1ull << 31)) {
+        set_err("reader_put: %llu memtable entries + %llu writes, at most "
+                "2^31 - 1 together (flush first)",
+                (unsigned long long)M.count, (unsigned long long)in.n);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (too_large != in.n) return batch_too_large("reader_put", too_large);
+    if (in.n == 0) return DBEEL_OK;
+
+    HIP_CHECK(hipSetDevice(rd->device));
+    hipStream_t s = rd->stream;
+    BatchStage b;
+    uint8_t* d_brun = nullptr;   /* B: 16 B pad | data | index | 16 B pad */
+    uint64_t* d_bpfx = nullptr;
+    uint8_t* d_merge = nullptr;  /* the merge's scratch, carved below      */
+    void* d_mtmp = nullptr;      /* its scans' rocPRIM scratch             */
+    ScopeGuard release([&] {
+        (void)hipStreamSynchronize(s);
+        batch_release(b);
+        (void)hipFree(d_brun);
+        (void)hipFree(d_bpfx);
+        (void)hipFree(d_merge);
+        (void)hipFree(d_mtmp);
+    });
+    rc = batch_order(b, in, s, rd->ev);
+    if (rc) return rc;
+
+    const uint64_t m = M.count, nb = b.n_surv;
+    ReaderMemtable::Buf& spare = M.buf[M.cur ^ 1];
+    uint64_t new_count = 0, new_len = 0;
+    if (m == 0) {
+        /* nothing to merge with: the ordered batch is the memtable */
+        HIP_CHECK(mem_reserve(spare, mem_run_bytes(b.total_bytes, nb), nb));
+        batch_encode(b, s, spare.d_run + 16, spare.d_run + 16 + b.total_bytes);
+        HIP_CHECK(hipEventRecord(rd->ev[3], s));
+        hipLaunchKernelGGL(k_reader_adopt, dim3(pick_grid(nb, 256)), dim3(256),
+                           0, s, spare.d_run + 16,
+                           spare.d_run + 16 + b.total_bytes, nb, spare.d_pfx,
+                           (uint32_t*)nullptr, (uint64_t)0, (uint64_t)0, 0u);
+        HIP_CHECK(hipEventRecord(rd->ev[4], s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        HIP_CHECK(hipGetLastError());
+        new_count = nb;
+        new_len = b.total_bytes;
+    } else {
+        /* stage 1 ends: B as a padded temporary run with its prefixes */
+        HIP_CHECK(hipMalloc(&d_brun, mem_run_bytes(b.total_bytes, nb)));
+        HIP_CHECK(hipMalloc(&d_bpfx, nb * sizeof(uint64_t)));
+        uint8_t* b_data = d_brun + 16;
+        uint8_t* b_index = b_data + b.total_bytes;
+        batch_encode(b, s, b_data, b_index);
+        hipLaunchKernelGGL(k_reader_adopt, dim3(pick_grid(nb, 256)), dim3(256),
+                           0, s, b_data, b_index, nb, d_bpfx,
+                           (uint32_t*)nullptr, (uint64_t)0, (uint64_t)0, 0u);
+        HIP_CHECK(hipEventRecord(rd->ev[3], s));
+
+        /* stage 2: merge B into M */
+        const uint64_t N = m + nb; /* < 2^31, checked above */
+        const uint64_t in_bytes = M.data_len + b.total_bytes;
+        RunsDesc D;
+        memset(&D, 0, sizeof D);
+        D.n_runs = 2;
+        D.total = N;
+        D.data[0] = M.data();
+        D.index[0] = M.index();
+        D.data_len[0] = M.data_len;
+        D.count[0] = m;
+        D.data[1] = b_data;
+        D.index[1] = b_index;
+        D.data_len[1] = b.total_bytes;
+        D.count[1] = nb;
+        D.entry_base[1] = m;
+        D.job_hi[0] = D.job_hi[1] = 2;
+        const MemPfx P = {{M.buf[M.cur].d_pfx, d_bpfx}};
+
+        uint64_t at = 0;
+        auto carve = [&](uint64_t bytes) {
+            const uint64_t o = at;
+            at += (bytes + 15) & ~15ull;
+            return o;
+        };
+        /* the window map is sized for the smallest copy window (8 KiB) */
+        const uint64_t o_rrec = carve(N * sizeof(RankRec)),
+                       o_dst = carve(N * 8), o_pos = carve(N * 4),
+                       o_oidx = carve(N * 16), o_smap = carve(N * 8),
+                       o_win = carve((in_bytes / 8192 + 2) * 4),
+                       o_tot = carve(sizeof(StepTotals)), o_err = carve(16);
+        HIP_CHECK(hipMalloc(&d_merge, at));
+        RankRec* d_rrec = (RankRec*)(d_merge + o_rrec);
+        uint64_t* d_dst = (uint64_t*)(d_merge + o_dst);
+        uint32_t* d_pos = (uint32_t*)(d_merge + o_pos);
+        uint8_t* d_oidx = d_merge + o_oidx;
+        uint64_t* d_smap = (uint64_t*)(d_merge + o_smap);
+        uint32_t* d_win = (uint32_t*)(d_merge + o_win);
+        StepTotals* d_tot = (StepTotals*)(d_merge + o_tot);
+        uint32_t* d_err = (uint32_t*)(d_merge + o_err);
+        size_t tmp_bytes = 0;
+        HIP_CHECK(survivor_scans(nullptr, tmp_bytes, d_rrec, d_dst, d_pos, N,
+                                 s));
+        HIP_CHECK(hipMalloc(&d_mtmp, tmp_bytes ? tmp_bytes : 1));
+        /* the spare is sized from the bound the totals are checked
+         * against below */
+        HIP_CHECK(mem_reserve(spare, mem_run_bytes(in_bytes, N), N));
+
+        HIP_CHECK(hipMemsetAsync(d_rrec, 0, N * sizeof(RankRec), s));
+        HIP_CHECK(hipMemsetAsync(d_tot, 0, o_err + 16 - o_tot, s));
+        hipLaunchKernelGGL(k_mem_rank, dim3(pick_grid(N, 256)), dim3(256), 0,
+                           s, D, P, d_rrec, d_err);
+        HIP_CHECK(survivor_scans(d_mtmp, tmp_bytes, d_rrec, d_dst, d_pos, N,
+                                 s));
+        hipLaunchKernelGGL(k_emit, dim3(pick_grid(N, 256)), dim3(256), 0, s, D,
+                           d_rrec, d_dst, d_pos, N, d_oidx, d_smap, d_err,
+                           d_tot);
+        HIP_CHECK(hipMemcpyAsync(&b.h->tot, d_tot, sizeof(StepTotals),
+                                 hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        HIP_CHECK(hipGetLastError());
+        new_count = b.h->tot.n_surv;
+        new_len = b.h->tot.total_out;
+        /* what the copy's stores are bounded by */
+        if (b.h->tot.err || new_count > N || new_count < (m > nb ? m : nb) ||
+            new_len > in_bytes || new_len < 32 * new_count) {
+            set_err("reader_put: merge totals %llu entries / %llu bytes are "
+                    "impossible for %llu + %llu entries (err %llu)",
+                    (unsigned long long)new_count,
+                    (unsigned long long)new_len, (unsigned long long)m,
+                    (unsigned long long)nb,
+                    (unsigned long long)b.h->tot.err);
+            return DBEEL_ERR_HIP;
+        }
+        uint8_t* n_data = spare.d_run + 16;
+        launch_copy(s, d_oidx, d_smap, d_win, d_tot, N, in_bytes, n_data);
+        HIP_CHECK(hipMemcpyAsync(n_data + new_len, d_oidx, new_count * 16,
+                                 hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL(k_reader_adopt, dim3(pick_grid(new_count, 256)),
+                           dim3(256), 0, s, n_data, n_data + new_len,
+                           new_count, spare.d_pfx, (uint32_t*)nullptr,
+                           (uint64_t)0, (uint64_t)0, 0u);
+        HIP_CHECK(hipEventRecord(rd->ev[4], s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        HIP_CHECK(hipGetLastError());
+    }
+    float ms[3] = {0, 0, 0};
+    HIP_CHECK(hipEventElapsedTime(&ms[0], rd->ev[0], rd->ev[1]));
+    HIP_CHECK(hipEventElapsedTime(&ms[1], rd->ev[1], rd->ev[3]));
+    HIP_CHECK(hipEventElapsedTime(&ms[2], rd->ev[3], rd->ev[4]));
+
+    /* the swap: from here the new memtable answers */
+    M.cur ^= 1;
+    M.count = new_count;
+    M.data_len = new_len;
+    M.puts++;
+    if (stats) {
+        stats->h2d_ms = ms[0];
+        stats->order_ms = ms[1];
+        stats->merge_ms = ms[2];
+        stats->writes_in = b.n;
+        stats->batch_entries = nb;
+        stats->replaced = m + nb - new_count;
+        stats->entries = new_count;
+        stats->data_bytes = new_len;
+        stats->prefix_tied = b.prefix_tied;
+    }
+    return DBEEL_OK;
+}
+
+extern "C" int dbeel_gpu_reader_memtable_info(const dbeel_gpu_reader* rd,
+                                              dbeel_memtable_info* info) {
+    g_err[0] = 0;
+    if (info) memset(info, 0, sizeof *info);
+    if (!rd || !info) {
+        set_err("reader_memtable_info: null argument");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    info->entries = rd->mem.count;
+    info->data_bytes = rd->mem.data_len;
+    info->reserved_bytes = rd->mem.reserved();
+    info->puts = rd->mem.puts;
+    return DBEEL_OK;
+}
+
+extern "C" int dbeel_gpu_reader_memtable_fetch(dbeel_gpu_reader* rd,
+                                               dbeel_compact_result* out) {
+    g_err[0] = 0;
+    if (out) memset(out, 0, sizeof *out);
+    if (!rd || !out) {
+        set_err("reader_memtable_fetch: null argument");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    const ReaderMemtable& M = rd->mem;
+    if (!M.count) return DBEEL_OK;
+    HIP_CHECK(hipSetDevice(rd->device));
+    return batch_fetch(M.data(), M.data_len, M.index(), M.count, rd->stream,
+                       out);
+}
+
+extern "C" void dbeel_gpu_reader_memtable_clear(dbeel_gpu_reader* rd) {
+    if (rd) rd->mem.drop();
+}
+
+extern "C" int dbeel_gpu_reader_memtable_flush(dbeel_gpu_reader* rd,
+                                               int build_bloom,
+                                               dbeel_compact_result* out,
+                                               uint8_t** bloom_bytes,
+                                               uint64_t* bloom_len) {
+    g_err[0] = 0;
+    if (out) memset(out, 0, sizeof *out);
+    if (bloom_bytes) *bloom_bytes = nullptr;
+    if (bloom_len) *bloom_len = 0;
+    if (!rd) {
+        set_err("reader_memtable_flush: null reader");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if ((bloom_bytes == nullptr) != (bloom_len == nullptr)) {
+        set_err("reader_memtable_flush: bloom_bytes and bloom_len go "
+                "together");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    ReaderMemtable& M = rd->mem;
+    if (!M.count) return DBEEL_OK; /* lsm_tree.rs:850-852 */
+    if (rd->tables.size() >= MAX_RUNS) {
+        set_err("reader_memtable_flush: reader already holds %d runs",
+                MAX_RUNS);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    HIP_CHECK(hipSetDevice(rd->device));
+    hipStream_t s = rd->stream;
+    ReaderTable t;
+    bool linked = false;
+    ScopeGuard release([&] {
+        if (linked) return;
+        (void)hipStreamSynchronize(s);
+        table_free(t);
+        if (out) dbeel_gpu_result_free(out);
+        if (bloom_bytes && *bloom_bytes) {
+            free(*bloom_bytes);
+            *bloom_bytes = nullptr;
+            *bloom_len = 0;
+        }
+    });
+    const uint64_t n_bits = build_bloom ? bloom_bits_for(M.count) : 0;
+    HIP_CHECK(table_alloc(t, M.data_len, M.count, n_bits));
+    HIP_CHECK(hipMemcpyAsync(t.d_run + 16, M.data(),
+                             M.data_len + M.count * 16,
+                             hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(table_adopt(t, n_bits, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipGetLastError());
+    if (out) {
+        int rc = batch_fetch(t.data(), t.data_len, t.index(), t.count, s, out);
+        if (rc) return rc;
+    }
+    if (bloom_bytes && n_bits) {
+        int rc = table_bloom_fetch(t, s, bloom_bytes, bloom_len);
+        if (rc) return rc;
+    }
+    /* the list edit of a push; on a failed link the edit is undone */
+    rd->tables.push_back(t);
+    hipError_t e = reader_link(rd);
+    if (e != hipSuccess) {
+        rd->tables.pop_back();
+        (void)reader_link(rd);
+        HIP_CHECK(e);
+    }
+    linked = true;
+    rd->generation++; /* open scans are stale from here on */
+    M.drop();
+    return DBEEL_OK;
+}
+
 extern "C" void dbeel_gpu_get_result_free(dbeel_get_result* r) {
     if (!r) return;
     free(r->hits);
@@ -4238,10 +4740,14 @@ extern "C" int dbeel_gpu_reader_get(dbeel_gpu_reader* rd,
     HIP_CHECK(hipMemsetAsync(rd->d_stats, 0, RS_N * sizeof(uint64_t), s));
     HIP_CHECK(hipMemsetAsync(d_hits + n, 0, sizeof(dbeel_lookup_hit), s));
     HIP_CHECK(hipEventRecord(rd->ev[1], s));
-    hipLaunchKernelGGL(k_reader_search, dim3(pick_grid(n, READER_BLOCK)),
-                       dim3(READER_BLOCK), 0, s, rd->desc, rd->pfx,
-                       rd->d_blooms, rd->d_keys, d_koff, n, d_hits,
-                       rd->d_stats);
+    void (*ks)(RunsDesc, ReaderPfx, ReaderMem, const ReaderBloom*,
+               const uint8_t*, const uint64_t*, uint64_t, dbeel_lookup_hit*,
+               unsigned long long*) = k_reader_search<false>;
+    if (rd->mem.count) ks = k_reader_search<true>;
+    hipLaunchKernelGGL(ks, dim3(pick_grid(n, READER_BLOCK)),
+                       dim3(READER_BLOCK),
+                       0, s, rd->desc, rd->pfx, rd->mem.view(), rd->d_blooms,
+                       rd->d_keys, d_koff, n, d_hits, rd->d_stats);
     HIP_CHECK(hipEventRecord(rd->ev[2], s));
     HIP_CHECK(rocprim::exclusive_scan(
         rd->d_scantmp, tmp_bytes,
@@ -4264,8 +4770,8 @@ extern "C" int dbeel_gpu_reader_get(dbeel_gpu_reader* rd,
     HIP_CHECK(hipEventRecord(rd->ev[4], s));
     if (total)
         hipLaunchKernelGGL(k_reader_gather, dim3(pick_grid(n * 64, 256)),
-                           dim3(256), 0, s, rd->desc, d_hits, d_voff, n,
-                           rd->d_values);
+                           dim3(256), 0, s, rd->desc, rd->mem.view().data,
+                           d_hits, d_voff, n, rd->d_values);
     HIP_CHECK(hipEventRecord(rd->ev[5], s));
     HIP_CHECK(hipMemcpyAsync(out->hits, d_hits, n * sizeof *out->hits,
                              hipMemcpyDeviceToHost, s));

@@ -631,6 +631,53 @@ extern "C" int dbeel_lsm_reader_flush(
     return DBEEL_OK;
 }
 
+extern "C" int dbeel_lsm_reader_memtable_flush(const char* dir_c,
+                                               dbeel_gpu_reader* rd,
+                                               uint64_t* indices, size_t* n,
+                                               uint64_t sstable_index) {
+    size_t pos = 0;
+    int rc = new_run_position(dir_c, rd, indices, n, sstable_index, &pos);
+    if (rc != DBEEL_OK) return rc;
+    /* the memtable flushes to the END of the list: the new table has to be
+     * the newest both in the reader and after a reopen */
+    if (pos != *n) {
+        dbeel_set_last_error("lsm_reader_memtable_flush: sstable_index must "
+                             "exceed every index held");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    std::string dp = file_path(dir_c, sstable_index, "data");
+    std::string ip = file_path(dir_c, sstable_index, "index");
+    if (exists(dp) || exists(ip)) {
+        dbeel_set_last_error("lsm_reader_memtable_flush: sstable files "
+                             "already exist");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    /* persist before linking: a file that cannot be written leaves the
+     * reader and the memtable as they were */
+    dbeel_compact_result res{};
+    rc = dbeel_gpu_reader_memtable_fetch(rd, &res);
+    /* an empty memtable flushes nothing (lsm_tree.rs:850-852) */
+    if (rc != DBEEL_OK || res.entries_written == 0) return rc;
+    bool ok = write_whole(dp, res.data, res.data_len) &&
+              write_whole(ip, res.index, res.index_len);
+    dbeel_gpu_result_free(&res);
+    if (ok) {
+        rc = dbeel_gpu_reader_memtable_flush(rd, /*build_bloom=*/0, nullptr,
+                                             nullptr, nullptr);
+    } else {
+        rc = DBEEL_ERR_IO;
+        dbeel_set_last_error("lsm_reader_memtable_flush: cannot write the "
+                             "sstable's data/index file");
+    }
+    if (rc != DBEEL_OK) {
+        unlink(dp.c_str());
+        unlink(ip.c_str());
+        return rc;
+    }
+    note_new_run(indices, n, pos, sstable_index);
+    return DBEEL_OK;
+}
+
 namespace {
 struct CommitArg {
     dbeel_gpu_reader* rd;

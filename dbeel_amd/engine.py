@@ -461,6 +461,37 @@ class WriteBatchStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class MemtablePutStats(ctypes.Structure):
+    """dbeel_memtable_put_stats."""
+    _fields_ = [
+        ("h2d_ms", ctypes.c_double),
+        ("order_ms", ctypes.c_double),
+        ("merge_ms", ctypes.c_double),
+        ("writes_in", ctypes.c_uint64),
+        ("batch_entries", ctypes.c_uint64),
+        ("replaced", ctypes.c_uint64),
+        ("entries", ctypes.c_uint64),
+        ("data_bytes", ctypes.c_uint64),
+        ("prefix_tied", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class MemtableInfo(ctypes.Structure):
+    """dbeel_memtable_info."""
+    _fields_ = [
+        ("entries", ctypes.c_uint64),
+        ("data_bytes", ctypes.c_uint64),
+        ("reserved_bytes", ctypes.c_uint64),
+        ("puts", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _U8P = ctypes.POINTER(ctypes.c_uint8)
 _U64P = ctypes.POINTER(ctypes.c_uint64)
 _BATCH_ARGTYPES = [ctypes.c_uint64, _U8P, _U64P, _U8P, _U64P, _U8P]
@@ -556,6 +587,22 @@ def _load_reader() -> ctypes.CDLL:
         lib.dbeel_gpu_flush_batch.restype = ctypes.c_int
         lib.dbeel_gpu_flush_batch.argtypes = _BATCH_ARGTYPES + [
             ctypes.c_int, ctypes.POINTER(CompactResult)]
+        lib.dbeel_gpu_reader_put.restype = ctypes.c_int
+        lib.dbeel_gpu_reader_put.argtypes = (
+            [ctypes.c_void_p] + _BATCH_ARGTYPES
+            + [ctypes.POINTER(MemtablePutStats)])
+        lib.dbeel_gpu_reader_memtable_info.restype = ctypes.c_int
+        lib.dbeel_gpu_reader_memtable_info.argtypes = [
+            ctypes.c_void_p, ctypes.POINTER(MemtableInfo)]
+        lib.dbeel_gpu_reader_memtable_fetch.restype = ctypes.c_int
+        lib.dbeel_gpu_reader_memtable_fetch.argtypes = [
+            ctypes.c_void_p, ctypes.POINTER(CompactResult)]
+        lib.dbeel_gpu_reader_memtable_flush.restype = ctypes.c_int
+        lib.dbeel_gpu_reader_memtable_flush.argtypes = [
+            ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(CompactResult),
+            ctypes.POINTER(_U8P), _U64P]
+        lib.dbeel_gpu_reader_memtable_clear.restype = None
+        lib.dbeel_gpu_reader_memtable_clear.argtypes = [ctypes.c_void_p]
         lib._reader_ready = True
     return lib
 
@@ -770,6 +817,85 @@ class Reader:
             if want_bloom:
                 self._lib.dbeel_gpu_bloom_free(bp)
         return data, index, bloom_bytes, st.as_dict()
+
+    def put(self, writes):
+        """Puts `writes` — (key, value, timestamp) in ARRIVAL order,
+        unsorted, keys may repeat, b"" is a tombstone — into the reader's
+        resident memtable: the last arrival of a key wins, across puts too,
+        whatever the timestamps. Gets see the memtable before every table
+        (hit["run"] == n_runs); scans do not. Returns the stats dict. An
+        empty batch changes nothing; on failure the memtable is
+        unchanged."""
+        if not self._h:
+            raise ValueError("reader is closed")
+        n, ptrs, keepalive = _write_arrays(writes)
+        st = MemtablePutStats()
+        rc = self._lib.dbeel_gpu_reader_put(self._h, n, *ptrs,
+                                            ctypes.byref(st))
+        del keepalive
+        self._check(rc)
+        return st.as_dict()
+
+    @property
+    def memtable_info(self) -> dict:
+        """entries / data_bytes held, reserved_bytes of device storage (not
+        part of table_bytes), puts since the last flush or clear."""
+        if not self._h:
+            raise ValueError("reader is closed")
+        info = MemtableInfo()
+        self._check(self._lib.dbeel_gpu_reader_memtable_info(
+            self._h, ctypes.byref(info)))
+        return info.as_dict()
+
+    def memtable_fetch(self):
+        """-> (data, index): the memtable's run bytes, what a flush would
+        write; (b"", b"") when it is empty. Changes nothing."""
+        if not self._h:
+            raise ValueError("reader is closed")
+        res = CompactResult()
+        self._check(self._lib.dbeel_gpu_reader_memtable_fetch(
+            self._h, ctypes.byref(res)))
+        try:
+            return (_ptr_bytes(res.data, res.data_len),
+                    _ptr_bytes(res.index, res.index_len))
+        finally:
+            self._lib.dbeel_gpu_result_free(ctypes.byref(res))
+
+    def memtable_flush(self, build_bloom: bool = False, fetch: bool = True):
+        """The memtable becomes the newest table (position n_runs) and is
+        empty afterwards. Returns (data, index, bloom_bytes): the run's file
+        bytes (None, None when fetch=False) and its "DBLM" filter bytes
+        (None unless build_bloom and fetch). An empty memtable flushes
+        nothing: (b"", b"", None)."""
+        if not self._h:
+            raise ValueError("reader is closed")
+        res = CompactResult()
+        bp = _U8P()
+        bn = ctypes.c_uint64()
+        want_bloom = bool(build_bloom) and fetch
+        rc = self._lib.dbeel_gpu_reader_memtable_flush(
+            self._h, int(build_bloom), ctypes.byref(res) if fetch else None,
+            ctypes.byref(bp) if want_bloom else None,
+            ctypes.byref(bn) if want_bloom else None)
+        self._check(rc)
+        data = index = bloom_bytes = None
+        try:
+            if fetch:
+                data = _ptr_bytes(res.data, res.data_len)
+                index = _ptr_bytes(res.index, res.index_len)
+            if want_bloom and bp:
+                bloom_bytes = _ptr_bytes(bp, int(bn.value))
+        finally:
+            if fetch:
+                self._lib.dbeel_gpu_result_free(ctypes.byref(res))
+            if want_bloom:
+                self._lib.dbeel_gpu_bloom_free(bp)
+        return data, index, bloom_bytes
+
+    def memtable_clear(self):
+        """Drop the memtable's contents; its device storage is kept."""
+        if self._h:
+            self._lib.dbeel_gpu_reader_memtable_clear(self._h)
 
     def compact_begin(self, positions, keep_tombstones: bool,
                       bloom: bool = False, fetch: bool = True):

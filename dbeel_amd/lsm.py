@@ -205,6 +205,28 @@ def reader_flush(dir: str, reader, indices, sstable_index: int, writes):
     return [int(idx[i]) for i in range(n.value)]
 
 
+def reader_memtable_flush(dir: str, reader, indices, sstable_index: int):
+    """The flush of the reader's resident memtable (Reader.put): its run is
+    fetched, written as {sstable_index:020}.data/.index (no .bloom) and
+    only then linked in as the newest table. sstable_index must exceed every
+    index held. Returns the new indices list; the reader then answers as a
+    fresh open_reader(dir) would. An empty memtable writes nothing; a file
+    that cannot be written leaves reader and memtable untouched."""
+    lib = load()
+    if not hasattr(lib, "_lsm_mem_flush_ready"):
+        lib.dbeel_lsm_reader_memtable_flush.restype = ctypes.c_int
+        lib.dbeel_lsm_reader_memtable_flush.argtypes = [
+            ctypes.c_char_p, ctypes.c_void_p,
+            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_size_t),
+            ctypes.c_uint64]
+        lib._lsm_mem_flush_ready = True
+    idx, n = _indices_array(indices)
+    rc = lib.dbeel_lsm_reader_memtable_flush(dir.encode(), reader._h, idx,
+                                             ctypes.byref(n), sstable_index)
+    _check(rc, lib)
+    return [int(idx[i]) for i in range(n.value)]
+
+
 def reader_compact(dir: str, reader, indices, compact_indices,
                    output_index: int, keep_tombstones: bool,
                    device_unused=None,

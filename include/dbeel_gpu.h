@@ -440,6 +440,99 @@ int dbeel_gpu_flush_batch(uint64_t n_writes, const uint8_t* keys,
         const uint64_t* value_offsets, const uint8_t* timestamps,
         int device, dbeel_compact_result* out);
 
+/* ---- Resident memtable: puts visible to gets, flushed as one run ----
+ * LSMTree::get_entry's first step (the active memtable, then the sstables
+ * newest-first, lsm_tree.rs:674-723) and the flush that ends it
+ * (lsm_tree.rs:850-915), with the memtable resident in HBM and owned by the
+ * reader.
+ *
+ * State: the memtable is ONE sorted run with unique keys in the resident
+ * table layout (16 B pad | data | index | 16 B pad, plus the dense 8-byte
+ * prefix array). It is not in the table list. Invariant: after puts
+ * W1 ... Wk since the last flush or clear, its data and index bytes are
+ * exactly dbeel_gpu_flush_batch(W1 || ... || Wk): one entry per distinct
+ * key, keys ascending bytewise, each with the value and timestamp of its
+ * LAST arrival whatever the timestamps are (the rbtree's set(),
+ * rbtree_arena/src/lib.rs:497-511), tombstones kept. An empty memtable
+ * changes nothing anywhere: every other call behaves, and reports
+ * table_bytes, exactly as without one.
+ *
+ * Get: dbeel_gpu_reader_get consults the memtable first
+ * (lsm_tree.rs:676-685). A key found there is a hit with
+ * run == dbeel_gpu_reader_run_count(reader) — the position the flush will
+ * give it; value_offset indexes the memtable's data bytes and is valid
+ * until the next put, flush or clear; is_tombstone and value_len work as for
+ * a table and the value bytes are packed into values like any other hit. A
+ * get just before memtable_flush and the same get just after return
+ * identical hits, offsets and value bytes. In dbeel_get_stats a non-empty
+ * memtable counts as one visit to an unfiltered run (searches).
+ *
+ * Liveness: a put does not edit the table list and bumps no generation, so
+ * open scans stay valid. Scans do NOT see the memtable (documented
+ * divergence from lsm_tree.rs:155-173: the caller flushes before
+ * migrating). A non-empty flush is a list edit at the end: open scans go
+ * stale, a pending compaction's positions do not move. A reader at 64
+ * tables still takes puts and answers from them (hit.run == 64);
+ * memtable_flush on it is DBEEL_ERR_INVALID_ARG and keeps the memtable. On
+ * any failure of any call below, the reader, its memtable and its answers
+ * are exactly as before.
+ *
+ * put: the arrays of dbeel_gpu_reader_write_batch, in arrival order. The
+ * batch is ordered and deduplicated by the write batch's own stages
+ * (DBEEL_BATCH_ORDER applies), then merged into the memtable on the device,
+ * the batch winning equal keys. Validated on the host before any device
+ * call, in this order: NULL reader, or a NULL array with n_writes != 0;
+ * n_writes >= 2^31; a descending offset; memtable entries + n_writes >=
+ * 2^31 (all DBEEL_ERR_INVALID_ARG); a write with 32 + klen + vlen >
+ * u32::MAX (DBEEL_ERR_ITEM_TOO_LARGE). n_writes == 0 is a successful no-op.
+ *
+ * Storage: a ping-pong pair of buffers that grows geometrically; a put
+ * writes the new memtable into the other buffer and swaps on success, and
+ * allocates only when it outgrows the pair. The pair is kept across flush
+ * and clear, freed by dbeel_gpu_reader_close, reported as
+ * memtable_info.reserved_bytes and not part of table_bytes. Staging and
+ * merge scratch belong to the call.
+ *
+ * fetch: copies the memtable's run bytes to the host (engine-allocated,
+ * dbeel_gpu_result_free) and changes nothing — for a caller that persists
+ * before it links. An empty memtable gives zeroed outputs and success.
+ *
+ * flush: an empty memtable is a no-op — no table, no generation change,
+ * zeroed outputs (lsm_tree.rs:850-852). Otherwise the memtable becomes a
+ * right-sized table at position n_runs (device-to-device copy; prefixes
+ * and, when build_bloom, a filter with dbeel_gpu_job_bloom's parameters in
+ * one pass), after which table_bytes equals a fresh reader's over the same
+ * runs, and the memtable is empty with its storage kept. out (NULL = leave
+ * the bytes on the device) and bloom_bytes / bloom_len (both NULL, or both
+ * set; free with dbeel_gpu_bloom_free) are what
+ * dbeel_gpu_reader_write_batch returns for the concatenated arrivals.
+ *
+ * clear: drops the contents, keeps the storage. */
+typedef struct {
+    double   h2d_ms, order_ms, merge_ms;  /* HIP events, reader stream: upload |
+                 prefixes + order + batch encode | rank, scans, emit, copy, prefixes */
+    uint64_t writes_in, batch_entries;    /* distinct keys in this batch          */
+    uint64_t replaced;                    /* memtable entries this batch overwrote */
+    uint64_t entries, data_bytes;         /* memtable after the put               */
+    uint64_t prefix_tied;                 /* as dbeel_write_batch_stats           */
+} dbeel_memtable_put_stats;
+
+typedef struct { uint64_t entries, data_bytes, reserved_bytes, puts; } dbeel_memtable_info;
+
+int  dbeel_gpu_reader_put(dbeel_gpu_reader* reader, uint64_t n_writes,
+        const uint8_t* keys, const uint64_t* key_offsets,
+        const uint8_t* values, const uint64_t* value_offsets,
+        const uint8_t* timestamps,
+        dbeel_memtable_put_stats* stats /* may be NULL */);
+int  dbeel_gpu_reader_memtable_info(const dbeel_gpu_reader* reader,
+        dbeel_memtable_info* info);
+int  dbeel_gpu_reader_memtable_fetch(dbeel_gpu_reader* reader,
+        dbeel_compact_result* out);
+int  dbeel_gpu_reader_memtable_flush(dbeel_gpu_reader* reader, int build_bloom,
+        dbeel_compact_result* out /* NULL = leave on device */,
+        uint8_t** bloom_bytes, uint64_t* bloom_len /* both or neither */);
+void dbeel_gpu_reader_memtable_clear(dbeel_gpu_reader* reader);
+
 /* ---- Resident-job API (benchmarking / repeated compactions) ----
  * Uploads the runs to `device` once; each run executes the device pipeline
  * with inputs already resident in HBM (what BASELINE's MB/s is quoted on)

@@ -127,7 +127,23 @@ int dbeel_lsm_reader_open(const char* dir, int device,
  * DBEEL_ERR_INVALID_ARG before anything is written; a file that cannot be
  * written is DBEEL_ERR_IO, with the table taken out of the reader again and
  * what was written removed. n_writes == 0 writes nothing and changes
- * nothing. */
+ * nothing.
+ *
+ * reader_memtable_flush: the flush of the reader's resident memtable
+ * (dbeel_gpu_reader_put, include/dbeel_gpu.h). dbeel_gpu_reader_memtable_fetch
+ * -> {sstable_index:020}.data / .index under their final names, no .bloom
+ * -> dbeel_gpu_reader_memtable_flush(out = NULL) -> sstable_index appended
+ * to indices. sstable_index must exceed every index held — the flushed
+ * table has to be the newest both in the reader and after a reopen —
+ * otherwise DBEEL_ERR_INVALID_ARG before anything is written. A file that
+ * cannot be written is DBEEL_ERR_IO: what was written is removed, and the
+ * reader and the memtable stay untouched (which is why the bytes are
+ * fetched first). An empty memtable writes nothing. The write-ahead log
+ * stays with the caller. */
+int dbeel_lsm_reader_memtable_flush(const char* dir,
+                                    struct dbeel_gpu_reader* reader,
+                                    uint64_t* indices, size_t* n,
+                                    uint64_t sstable_index);
 int dbeel_lsm_reader_add(const char* dir, struct dbeel_gpu_reader* reader,
                          uint64_t* indices, size_t* n,
                          uint64_t sstable_index);

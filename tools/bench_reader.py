@@ -152,8 +152,10 @@ def merge_kernel_stats(csv_path, out_path):
     with open(csv_path, newline="") as f:
         for row in csv.DictReader(f):
             name = row.get("Name", "")
+            if name.startswith("void "):  # a template instantiation
+                name = name[5:]
             for key, label in want.items():
-                if name.startswith(key + "(") or name == key:
+                if name.startswith((key + "(", key + "<")) or name == key:
                     found[label] = {
                         "calls": int(row["Calls"]),
                         "avg_ms": float(row["AverageNs"]) / 1e6,

@@ -4,7 +4,9 @@ streamed ingests (each creates ~per-chunk HIP events), batched jobs,
 scans, sliced compactions and resident readers (open / get x N / paged
 scans begin + next + end, one left for close to end / insert / compact
 begin + abort + commit / write batches with fetch on and off, a filter,
-both order paths and a refused call / close), reporting hipMemGetInfo
+both order paths and a refused call / memtable put x N + get + fetch +
+flush + clear, with the storage pair checked never to shrink nor to regrow
+after a flush / close with a non-empty memtable), reporting hipMemGetInfo
 drift. A leak in any path shows as monotonically shrinking free memory.
 
     python tools/leakcheck.py --iters 40
@@ -135,6 +137,27 @@ def main():
                 except DbeelGpuError:
                     pass
                 rd.get(probe_keys[:4000])
+                # resident memtable: put x N (the ping-pong pair grows in
+                # the first iteration's first puts only — a reader is new
+                # each iteration, so its growth recurs but is freed by
+                # close) / get / fetch / flush / clear, and close with a
+                # non-empty memtable
+                reserved = 0
+                for lo in range(0, len(batch), 4000):
+                    rd.put(batch[lo:lo + 4000])
+                    now = rd.memtable_info["reserved_bytes"]
+                    if now < reserved:
+                        raise SystemExit("memtable storage shrank")
+                    reserved = now
+                rd.get(probe_keys[:4000])
+                rd.memtable_fetch()
+                rd.memtable_flush(build_bloom=True)
+                rd.put(batch[:3000])
+                rd.memtable_clear()
+                rd.put(batch[::2])
+                if rd.memtable_info["reserved_bytes"] != reserved:
+                    raise SystemExit("memtable storage regrew after a flush")
+                rd.get(probe_keys[:1000])  # close frees the memtable
             flush_batch(batch[:7000], device=0)
             f = free_mem()
             if base is None:
