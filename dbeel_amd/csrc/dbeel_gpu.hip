@@ -51,7 +51,10 @@
  *                  a compaction output into a resident table (prefixes
  *                  + filter bits in one pass) for the live table list;
  *                  k_reader_scan_bounds/_flag/_emit page the migration
- *                  scan over the resident tables into caller buffers.
+ *                  scan over the resident tables into caller buffers;
+ *                  k_reader_scan_shadow (snapshot scans with
+ *                  DBEEL_SCAN_NEWEST_ONLY) drops the candidates whose key
+ *                  a later table or the memtable holds.
  *   k_batch_*    : the memtable + flush for the reader: an unsorted
  *                  write batch is ordered (one rocPRIM merge sort on
  *                  (prefix, key, arrival); or a radix sort on the prefix
@@ -2903,6 +2906,11 @@ struct ReaderTable {
     uint64_t data_len = 0, count = 0;
     ReaderBloom bloom{};        /* header fields; .bits == d_bits        */
     uint64_t bytes = 0;         /* requested bytes: run + prefixes + bitmap */
+    /* holders of the three buffers: the list plus every snapshot scan that
+     * reads them. NULL = the list alone (no snapshot has held the table
+     * yet); allocated by the first snapshot, shared by every copy of this
+     * struct, freed with the buffers by the last holder (table_free). */
+    uint32_t* refs = nullptr;
 
     const uint8_t* data() const { return d_run + 16; }
     const uint8_t* index() const { return d_run + 16 + data_len; }
@@ -2916,22 +2924,40 @@ struct ScanPageTotals {
     uint64_t next;      /* window position of the first survivor not taken,
                            or the window length when all were taken        */
     uint64_t next_full; /* that survivor's full_size, 0 when there is none  */
+    uint64_t shadowed;  /* NEWEST_ONLY: shadowed candidates among the first
+                           `next`; not written by k_reader_scan_emit        */
 };
 
 struct dbeel_gpu_reader_scan;
+
+/* A memtable buffer that snapshot scans read. While in_pair it is still one
+ * of the ping-pong pair and counts in reserved_bytes; a put that would write
+ * into it hands it over instead (in_pair = false, the pair takes a fresh
+ * buffer) and it then lives, counted in held_bytes, until its last scan
+ * ends. */
+struct MemHold {
+    uint8_t* d_run = nullptr;
+    uint64_t* d_pfx = nullptr;
+    uint64_t bytes = 0; /* run_cap + pfx_cap */
+    uint32_t refs = 0;  /* scans */
+    bool in_pair = true;
+};
 
 /* The resident memtable: one sorted run with unique keys in the table
  * layout (16 B pad | data | index | 16 B pad, plus the dense prefix array),
  * held in buf[cur]. A put builds its successor in buf[cur ^ 1] and swaps on
  * success, so a failed put leaves it untouched. The pair grows
  * geometrically and is kept across flush and clear; none of it counts in
- * table_bytes. */
+ * table_bytes. A buffer that snapshot scans read (hold) is never written:
+ * the put that would hands it over to them and puts a fresh one in its
+ * place. */
 struct ReaderMemtable {
     struct Buf {
         uint8_t* d_run = nullptr;
         uint64_t run_cap = 0; /* bytes */
         uint64_t* d_pfx = nullptr;
         uint64_t pfx_cap = 0; /* bytes */
+        MemHold* hold = nullptr; /* set while snapshot scans read it */
     } buf[2];
     int cur = 0;
     uint64_t count = 0, data_len = 0, puts = 0;
@@ -2964,8 +2990,8 @@ struct dbeel_gpu_reader {
     bool has_pending = false;
     ReaderTable pending;
     std::vector<uint32_t> pending_pos; /* its input tables, ascending    */
-    /* puts not flushed yet; gets consult it before every table, scans do
-     * not see it */
+    /* puts not flushed yet; gets consult it before every table, scans see
+     * it only when opened as snapshots with DBEEL_SCAN_MEMTABLE */
     ReaderMemtable mem;
     /* per-batch scratch, grown on demand and reused */
     uint8_t* d_keys = nullptr;
@@ -3006,7 +3032,15 @@ static hipError_t reader_reserve(void** p, uint64_t* cap, uint64_t need) {
     return e;
 }
 
+/* Lets go of one holder's reference; the last one frees the buffers. */
 static void table_free(ReaderTable& t) {
+    if (t.refs) {
+        if (--*t.refs) {
+            t = ReaderTable();
+            return;
+        }
+        delete t.refs;
+    }
     (void)hipFree(t.d_run);
     (void)hipFree(t.d_pfx);
     (void)hipFree(t.d_bits);
@@ -4402,6 +4436,13 @@ extern "C" int dbeel_gpu_reader_put(dbeel_gpu_reader* rd, uint64_t n_writes,
     uint64_t* d_bpfx = nullptr;
     uint8_t* d_merge = nullptr;  /* the merge's scratch, carved below      */
     void* d_mtmp = nullptr;      /* its scans' rocPRIM scratch             */
+    /* a spare that snapshot scans still read is not written: the new
+     * memtable goes into a fresh buffer, and at the swap the held one is
+     * handed over to its scans while the fresh one joins the pair. Until
+     * then nothing has changed, so a failed put leaves every count as it
+     * was. */
+    ReaderMemtable::Buf fresh;
+    const bool displace = M.buf[M.cur ^ 1].hold != nullptr;
     ScopeGuard release([&] {
         (void)hipStreamSynchronize(s);
         batch_release(b);
@@ -4409,12 +4450,14 @@ extern "C" int dbeel_gpu_reader_put(dbeel_gpu_reader* rd, uint64_t n_writes,
         (void)hipFree(d_bpfx);
         (void)hipFree(d_merge);
         (void)hipFree(d_mtmp);
+        (void)hipFree(fresh.d_run);
+        (void)hipFree(fresh.d_pfx);
     });
     rc = batch_order(b, in, s, rd->ev);
     if (rc) return rc;
 
     const uint64_t m = M.count, nb = b.n_surv;
-    ReaderMemtable::Buf& spare = M.buf[M.cur ^ 1];
+    ReaderMemtable::Buf& spare = displace ? fresh : M.buf[M.cur ^ 1];
     uint64_t new_count = 0, new_len = 0;
     if (m == 0) {
         /* nothing to merge with: the ordered batch is the memtable */
@@ -4534,6 +4577,13 @@ extern "C" int dbeel_gpu_reader_put(dbeel_gpu_reader* rd, uint64_t n_writes,
     HIP_CHECK(hipEventElapsedTime(&ms[2], rd->ev[3], rd->ev[4]));
 
     /* the swap: from here the new memtable answers */
+    if (displace) {
+        ReaderMemtable::Buf& old = M.buf[M.cur ^ 1];
+        old.hold->bytes = old.run_cap + old.pfx_cap;
+        old.hold->in_pair = false; /* its scans free it */
+        old = fresh;
+        fresh = ReaderMemtable::Buf();
+    }
     M.cur ^= 1;
     M.count = new_count;
     M.data_len = new_len;
@@ -5175,20 +5225,270 @@ __global__ void k_reader_scan_emit(RunsDesc R, const RankRec* rrec,
     }
 }
 
+/* ---- DBEEL_SCAN_NEWEST_ONLY: the shadow pass ----
+ * Runs between k_reader_scan_flag and the survivor scans and clears RR_KEEP
+ * on every kept window record whose key a LATER segment of the snapshot
+ * holds: the memtable first (a ReaderMem leg like mem_search), then tables
+ * n-1 .. r+1, stopping at the first match. Each table probe has
+ * k_reader_search's shape — filter check with the hash pair computed once
+ * per seed, bisection of the dense prefix array, then the equal-prefix
+ * stretch settled by bisection with full key compares, never a walk.
+ *
+ * NARROW (DBEEL_SCAN_SHADOW=narrow; not the default — it measured level
+ * with the plain pass): the window's candidates are consecutive entries of sorted tables,
+ * so a tile of SHADOW_BLOCK consecutive candidates of ONE table can only
+ * match inside [lower_bound(prefix of its first key), upper_bound(prefix of
+ * its last key)) of each later segment. One thread per later segment (at
+ * most 64 tables + the memtable) bisects those two bounds into LDS once per
+ * tile, and every lane then bisects the narrowed slice only. A tile that
+ * straddles a table boundary, and a lane whose prefix lies outside the
+ * tile's bounds, use the full bisection. LDS: 65 * 16 B = 1040 B per block;
+ * at 256 threads the block's occupancy is set by registers, not LDS. */
+#define SHADOW_BLOCK 256
+#define SHADOW_SEGS (MAX_RUNS + 1) /* slot MAX_RUNS = the memtable */
+
+/* Is (key, klen) in table r? Prefix bisection confined to [blo, bhi). */
+__device__ __forceinline__ bool table_has_key(const RunsDesc& R,
+                                              const uint64_t* P, int r,
+                                              uint64_t blo, uint64_t bhi,
+                                              const uint8_t* key,
+                                              uint64_t klen, uint64_t qp) {
+    uint64_t lo = blo + pfx_lower_bound(P + blo, bhi - blo, qp);
+    if (lo >= bhi || P[lo] != qp) return false;
+    uint64_t end = lo + 1;
+    if (end < bhi && P[end] == qp) end = pfx_upper_bound(P, end + 1, bhi, qp);
+    while (lo < end) {
+        const uint64_t mid = (lo + end) >> 1;
+        EView m;
+        if (!load_entry(R, r, mid, m)) { /* validated at open */
+            end = mid;
+            continue;
+        }
+        const int cmp = cmp_keys(m.key, m.klen, key, klen);
+        if (cmp == 0) return true;
+        if (cmp < 0)
+            lo = mid + 1;
+        else
+            end = mid;
+    }
+    return false;
+}
+
+template <bool NARROW>
+__global__ __launch_bounds__(SHADOW_BLOCK) void k_reader_scan_shadow(
+    RunsDesc R, ReaderPfx pfx, ReaderMem mem, const ReaderBloom* blooms,
+    uint64_t m, RankRec* rrec) {
+    __shared__ uint64_t s_lo[SHADOW_SEGS], s_hi[SHADOW_SEGS];
+    __shared__ int s_tile_run; /* the tile's table, -1 = straddles */
+    __shared__ uint64_t s_pf, s_pl;
+    const uint64_t n_tiles = (m + SHADOW_BLOCK - 1) / SHADOW_BLOCK;
+    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint64_t w0 = tile * SHADOW_BLOCK;
+        const uint64_t w = w0 + threadIdx.x;
+        if constexpr (NARROW) {
+            __syncthreads(); /* the previous tile's bounds are done with */
+            const uint64_t wl =
+                (w0 + SHADOW_BLOCK <= m ? w0 + SHADOW_BLOCK : m) - 1;
+            const RankRec a = rrec[w0], z = rrec[wl];
+            const int ra = (int)((a.src >> 48) & 0x7FFF);
+            const int rz = (int)((z.src >> 48) & 0x7FFF);
+            const uint64_t pf = key_prefix(
+                R.data[ra] + (a.src & RR_OFF_MASK) + 8, a.key_size - 8);
+            const uint64_t pl = key_prefix(
+                R.data[rz] + (z.src & RR_OFF_MASK) + 8, z.key_size - 8);
+            if (threadIdx.x == 0) {
+                s_tile_run = ra == rz ? ra : -1;
+                s_pf = pf;
+                s_pl = pl;
+            }
+            const int t = (int)threadIdx.x;
+            if (ra == rz && t < SHADOW_SEGS) {
+                const uint64_t* P = nullptr;
+                uint64_t n = 0;
+                if (t == MAX_RUNS) {
+                    P = mem.pfx;
+                    n = mem.count;
+                } else if (t > ra && t < R.n_runs) {
+                    P = pfx.p[t];
+                    n = R.count[t];
+                }
+                uint64_t lo = 0, hi = 0;
+                if (n) {
+                    lo = pfx_lower_bound(P, n, pf);
+                    hi = pfx_upper_bound(P, lo, n, pl);
+                }
+                s_lo[t] = lo;
+                s_hi[t] = hi;
+            }
+            __syncthreads();
+        }
+        if (w >= m) continue;
+        const RankRec rec = rrec[w];
+        if (!(rec.src & RR_KEEP)) continue;
+        const int r = (int)((rec.src >> 48) & 0x7FFF);
+        const uint8_t* key = R.data[r] + (rec.src & RR_OFF_MASK) + 8;
+        const uint64_t klen = rec.key_size - 8;
+        const uint64_t qp = key_prefix(key, klen);
+        bool narrow = false;
+        if constexpr (NARROW)
+            narrow = s_tile_run == r && qp >= s_pf && qp <= s_pl;
+        bool shadowed = false;
+        if (mem.count) {
+            uint64_t off, vlen;
+            if (narrow) {
+                /* the index records hold offsets into data: a slice of the
+                 * index and prefix arrays is a memtable of its own */
+                const uint64_t lo = s_lo[MAX_RUNS], hi = s_hi[MAX_RUNS];
+                const ReaderMem sl = {mem.data, mem.index + lo * 16,
+                                      mem.pfx + lo, hi - lo};
+                shadowed = mem_search(sl, key, klen, qp, off, vlen);
+            } else {
+                shadowed = mem_search(mem, key, klen, qp, off, vlen);
+            }
+        }
+        bool have_hash = false;
+        uint64_t hseed = 0, h1 = 0, h2 = 0;
+        for (int t = R.n_runs - 1; t > r && !shadowed; t--) {
+            const uint64_t n = R.count[t];
+            uint64_t blo = 0, bhi = n;
+            if (narrow) {
+                blo = s_lo[t];
+                bhi = s_hi[t];
+            }
+            if (blo >= bhi) continue;
+            const ReaderBloom B = blooms[t];
+            if (B.bits) {
+                if (!have_hash || hseed != B.seed) {
+                    hseed = B.seed;
+                    h1 = d_fnv1a64(key, klen, hseed);
+                    h2 = d_fnv1a64(key, klen,
+                                   hseed ^ 0x9e3779b97f4a7c15ull) | 1;
+                    have_hash = true;
+                }
+                bool maybe = true;
+                for (uint32_t j = 0; j < B.k; j++) {
+                    const uint64_t bit = (h1 + j * h2) % B.n_bits;
+                    if (!(B.bits[bit >> 3] & (1u << (bit & 7)))) {
+                        maybe = false;
+                        break;
+                    }
+                }
+                if (!maybe) continue;
+            }
+            shadowed = table_has_key(R, pfx.p[t], t, blo, bhi, key, klen, qp);
+        }
+        if (shadowed) rrec[w].src = rec.src & ~RR_KEEP;
+    }
+}
+
+/* Shadowed candidates among the first tot->next of the window — the ones
+ * the page consumed; the caps may cut a window short, and what lies past
+ * the cut is examined again by the next page. A candidate that passed the
+ * hash filter and is not kept was cleared by the shadow pass. Block
+ * reduction, then one atomic per block. */
+__global__ __launch_bounds__(256) void k_reader_scan_shadow_count(
+    const RankRec* rrec, const uint32_t* rid, uint32_t n_ranges,
+    ScanPageTotals* tot) {
+    __shared__ unsigned long long s_sum;
+    if (threadIdx.x == 0) s_sum = 0;
+    __syncthreads();
+    const uint64_t n = tot->next;
+    unsigned long long c = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < n;
+         g += stride)
+        if (!(rrec[g].src & RR_KEEP) &&
+            (n_ranges == 0 || rid[g] != SCAN_NO_RANGE))
+            c++;
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_sum, c);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_sum)
+        atomicAdd((unsigned long long*)&tot->shadowed, s_sum);
+}
+
 struct dbeel_gpu_reader_scan {
     dbeel_gpu_reader* rd = nullptr;
     uint64_t generation = 0; /* rd->generation at begin */
     ScanWin win{};
-    uint64_t total = 0;  /* candidates in all tables */
+    uint64_t total = 0;  /* candidates in all segments */
     uint64_t cursor = 0; /* next candidate to examine */
     uint64_t max_candidates = 0;
     uint32_t* d_ranges = nullptr; /* starts | ends */
     uint32_t n_ranges = 0;
+    uint32_t n_tables = 0;        /* tables in the list at begin */
+    uint64_t table_total = 0;     /* candidates in the tables */
+    /* snapshot scans (dbeel_gpu_reader_scan_snapshot): what the kernels saw
+     * of the list at begin, a reference to every table of it, and — with
+     * DBEEL_SCAN_MEMTABLE and a non-empty memtable — the memtable of that
+     * moment as the last segment: candidates [table_total, total), entry
+     * mem_lo + (c - table_total). Nothing here follows a list edit. */
+    bool snapshot = false;
+    uint32_t flags = 0;
+    RunsDesc desc{};
+    ReaderPfx pfx{};
+    ReaderBloom* d_blooms = nullptr; /* NEWEST_ONLY: the filters at begin */
+    std::vector<ReaderTable> held;
+    MemHold* mem_hold = nullptr;
+    ReaderMem mem{};
+    uint64_t mem_data_len = 0, mem_lo = 0;
+    uint64_t shadowed = 0;
 };
 
 static void scan_free(dbeel_gpu_reader_scan* sc) {
     (void)hipFree(sc->d_ranges);
+    (void)hipFree(sc->d_blooms);
+    for (ReaderTable& t : sc->held) table_free(t);
+    if (MemHold* h = sc->mem_hold) {
+        if (--h->refs == 0) {
+            if (h->in_pair) {
+                for (ReaderMemtable::Buf& b : sc->rd->mem.buf)
+                    if (b.hold == h) b.hold = nullptr;
+            } else {
+                (void)hipFree(h->d_run);
+                (void)hipFree(h->d_pfx);
+            }
+            delete h;
+        }
+    }
     delete sc;
+}
+
+extern "C" uint64_t dbeel_gpu_reader_held_bytes(const dbeel_gpu_reader* rd) {
+    if (!rd) return 0;
+    /* each buffer once, however many scans hold it */
+    std::vector<const void*> seen;
+    uint64_t sum = 0;
+    auto first_time = [&](const void* p) {
+        for (const void* q : seen)
+            if (q == p) return false;
+        seen.push_back(p);
+        return true;
+    };
+    for (const ReaderTable& t : rd->tables) seen.push_back(t.d_run);
+    for (const dbeel_gpu_reader_scan* sc : rd->scans) {
+        for (const ReaderTable& t : sc->held)
+            if (first_time(t.d_run)) sum += t.bytes;
+        const MemHold* h = sc->mem_hold;
+        if (h && !h->in_pair && first_time(h)) sum += h->bytes;
+    }
+    return sum;
+}
+
+extern "C" int dbeel_gpu_reader_scan_info(const dbeel_gpu_reader_scan* sc,
+                                          dbeel_scan_snapshot_info* info) {
+    g_err[0] = 0;
+    if (info) memset(info, 0, sizeof *info);
+    if (!sc || !info) {
+        set_err("reader_scan_info: null argument");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    info->n_tables = sc->n_tables;
+    info->has_memtable = sc->mem.count ? 1 : 0;
+    info->table_candidates = sc->table_total;
+    info->memtable_candidates = sc->total - sc->table_total;
+    info->shadowed = sc->shadowed;
+    return DBEEL_OK;
 }
 
 static void reader_end_scans(dbeel_gpu_reader* rd) {
@@ -5208,27 +5508,27 @@ extern "C" void dbeel_gpu_reader_scan_end(dbeel_gpu_reader_scan* sc) {
     scan_free(sc);
 }
 
-extern "C" int dbeel_gpu_reader_scan_begin(
+/* begin of both kinds of scan; fn names the entry point in messages. The
+ * checks are host-only and come before any device call. */
+static int scan_begin_impl(const char* fn, bool snapshot, uint32_t flags,
     dbeel_gpu_reader* rd, const uint8_t* start_key, size_t start_key_len,
     const uint8_t* end_key, size_t end_key_len, const uint32_t* range_starts,
     const uint32_t* range_ends, size_t n_ranges, uint64_t max_candidates,
     dbeel_gpu_reader_scan** out) {
-    g_err[0] = 0;
-    if (out) *out = nullptr;
     if (!rd || !out) {
-        set_err("reader_scan_begin: null reader or out");
+        set_err("%s: null reader or out", fn);
         return DBEEL_ERR_INVALID_ARG;
     }
     if ((start_key_len && !start_key) || (end_key_len && !end_key)) {
-        set_err("reader_scan_begin: key length given without its pointer");
+        set_err("%s: key length given without its pointer", fn);
         return DBEEL_ERR_INVALID_ARG;
     }
     if (n_ranges && (!range_starts || !range_ends)) {
-        set_err("reader_scan_begin: n_ranges given without the range arrays");
+        set_err("%s: n_ranges given without the range arrays", fn);
         return DBEEL_ERR_INVALID_ARG;
     }
     if (n_ranges >= SCAN_NO_RANGE) {
-        set_err("reader_scan_begin: too many hash ranges");
+        set_err("%s: too many hash ranges", fn);
         return DBEEL_ERR_INVALID_ARG;
     }
     HIP_CHECK(hipSetDevice(rd->device));
@@ -5249,11 +5549,41 @@ extern "C" int dbeel_gpu_reader_scan_begin(
                                         : SCAN_DEFAULT_CANDIDATES;
     if (sc->max_candidates > SCAN_MAX_CANDIDATES)
         sc->max_candidates = SCAN_MAX_CANDIDATES;
+    sc->snapshot = snapshot;
+    sc->flags = flags;
 
     const int n_runs = rd->desc.n_runs;
+    sc->n_tables = (uint32_t)n_runs;
+    const bool want_mem =
+        snapshot && (flags & DBEEL_SCAN_MEMTABLE) && rd->mem.count;
+    /* host allocations of the snapshot come first: past them only device
+     * calls can fail, and those change nothing of the reader */
+    MemHold* new_hold = nullptr;
+    if (snapshot) {
+        bool ok = true;
+        try {
+            sc->held.reserve(rd->tables.size());
+        } catch (...) {
+            ok = false;
+        }
+        for (ReaderTable& t : rd->tables)
+            if (ok && !t.refs) {
+                t.refs = new (std::nothrow) uint32_t(1); /* the list */
+                ok = t.refs != nullptr;
+            }
+        if (ok && want_mem && !rd->mem.buf[rd->mem.cur].hold) {
+            new_hold = new (std::nothrow) MemHold();
+            ok = new_hold != nullptr;
+        }
+        if (!ok) {
+            set_err("host alloc failed");
+            scan_free(sc);
+            return DBEEL_ERR_OOM;
+        }
+    }
     const uint64_t kb_len = (uint64_t)start_key_len + end_key_len;
-    uint64_t hb[2 * MAX_RUNS];
-    uint8_t* d_kb = nullptr; /* bound keys | 2 * n_runs bounds, 8-B aligned */
+    uint64_t hb[2 * MAX_RUNS + 2]; /* tables, then the memtable segment */
+    uint8_t* d_kb = nullptr; /* bound keys | the bounds, 8-B aligned */
     const uint64_t kb_pad = (kb_len + 7) & ~7ull;
     hipError_t e = hipSuccess;
     if (n_ranges) {
@@ -5265,7 +5595,15 @@ extern "C" int dbeel_gpu_reader_scan_begin(
             e = hipMemcpyAsync(sc->d_ranges + n_ranges, range_ends,
                                n_ranges * 4, hipMemcpyHostToDevice, s);
     }
-    if (e == hipSuccess && n_runs) {
+    if (e == hipSuccess && snapshot && (flags & DBEEL_SCAN_NEWEST_ONLY)) {
+        /* rd->d_blooms is rewritten by every list edit */
+        e = hipMalloc(&sc->d_blooms, MAX_RUNS * sizeof(ReaderBloom));
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(sc->d_blooms, rd->d_blooms,
+                               MAX_RUNS * sizeof(ReaderBloom),
+                               hipMemcpyDeviceToDevice, s);
+    }
+    if (e == hipSuccess && (n_runs || want_mem)) {
         e = hipMalloc(&d_kb, kb_pad + sizeof hb);
         if (e == hipSuccess && start_key_len)
             e = hipMemcpyAsync(d_kb, start_key, start_key_len,
@@ -5273,8 +5611,8 @@ extern "C" int dbeel_gpu_reader_scan_begin(
         if (e == hipSuccess && end_key_len)
             e = hipMemcpyAsync(d_kb + start_key_len, end_key, end_key_len,
                                hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) {
-            uint64_t* d_bounds = (uint64_t*)(d_kb + kb_pad);
+        uint64_t* d_bounds = (uint64_t*)(d_kb + kb_pad);
+        if (e == hipSuccess && n_runs) {
             hipLaunchKernelGGL(k_reader_scan_bounds, dim3(1),
                                dim3(2 * MAX_RUNS), 0, s, rd->desc, rd->pfx,
                                d_kb, (uint64_t)start_key_len,
@@ -5284,6 +5622,31 @@ extern "C" int dbeel_gpu_reader_scan_begin(
                                2 * (size_t)n_runs * sizeof(uint64_t),
                                hipMemcpyDeviceToHost, s);
         }
+        if (e == hipSuccess && want_mem) {
+            /* the memtable segment's bounds: the same bisection over its
+             * own prefix array, as a table list of one */
+            const ReaderMemtable& M = rd->mem;
+            RunsDesc D1;
+            memset(&D1, 0, sizeof D1);
+            D1.n_runs = 1;
+            D1.total = M.count;
+            D1.data[0] = M.data();
+            D1.index[0] = M.index();
+            D1.data_len[0] = M.data_len;
+            D1.count[0] = M.count;
+            D1.job_hi[0] = 1;
+            ReaderPfx P1;
+            memset(&P1, 0, sizeof P1);
+            P1.p[0] = M.buf[M.cur].d_pfx;
+            hipLaunchKernelGGL(k_reader_scan_bounds, dim3(1),
+                               dim3(2 * MAX_RUNS), 0, s, D1, P1, d_kb,
+                               (uint64_t)start_key_len, (uint64_t)end_key_len,
+                               start_key ? 1 : 0, end_key ? 1 : 0,
+                               d_bounds + 2 * MAX_RUNS);
+            e = hipMemcpyAsync(hb + 2 * MAX_RUNS, d_bounds + 2 * MAX_RUNS,
+                               2 * sizeof(uint64_t), hipMemcpyDeviceToHost,
+                               s);
+        }
     }
     /* the caller's keys and ranges are read by the async copies above */
     hipError_t se = hipStreamSynchronize(s);
@@ -5291,7 +5654,8 @@ extern "C" int dbeel_gpu_reader_scan_begin(
     if (e == hipSuccess) e = hipGetLastError();
     (void)hipFree(d_kb);
     if (e != hipSuccess) {
-        set_err("reader_scan_begin: %s", hipGetErrorString(e));
+        set_err("%s: %s", fn, hipGetErrorString(e));
+        delete new_hold;
         scan_free(sc);
         return e == hipErrorOutOfMemory ? DBEEL_ERR_OOM : DBEEL_ERR_HIP;
     }
@@ -5306,10 +5670,68 @@ extern "C" int dbeel_gpu_reader_scan_begin(
         base += hi - lo;
         sc->win.cend[r] = base;
     }
+    sc->table_total = base;
+    if (snapshot) {
+        /* nothing can fail from here: take the references */
+        sc->desc = rd->desc;
+        sc->pfx = rd->pfx;
+        for (ReaderTable& t : rd->tables) {
+            ++*t.refs;
+            sc->held.push_back(t);
+        }
+    }
+    if (want_mem) {
+        ReaderMemtable& M = rd->mem;
+        ReaderMemtable::Buf& cur = M.buf[M.cur];
+        if (!cur.hold) {
+            new_hold->d_run = cur.d_run;
+            new_hold->d_pfx = cur.d_pfx;
+            cur.hold = new_hold;
+        }
+        cur.hold->refs++;
+        sc->mem_hold = cur.hold;
+        sc->mem = M.view();
+        sc->mem_data_len = M.data_len;
+        uint64_t lo = hb[2 * MAX_RUNS], hi = hb[2 * MAX_RUNS + 1];
+        if (lo > M.count) lo = M.count;
+        if (hi > M.count) hi = M.count;
+        if (hi < lo) hi = lo;
+        sc->mem_lo = lo;
+        base += hi - lo;
+    }
     sc->total = base;
     rd->scans.push_back(sc);
     *out = sc;
     return DBEEL_OK;
+}
+
+extern "C" int dbeel_gpu_reader_scan_begin(
+    dbeel_gpu_reader* rd, const uint8_t* start_key, size_t start_key_len,
+    const uint8_t* end_key, size_t end_key_len, const uint32_t* range_starts,
+    const uint32_t* range_ends, size_t n_ranges, uint64_t max_candidates,
+    dbeel_gpu_reader_scan** out) {
+    g_err[0] = 0;
+    if (out) *out = nullptr;
+    return scan_begin_impl("reader_scan_begin", false, 0, rd, start_key,
+                           start_key_len, end_key, end_key_len, range_starts,
+                           range_ends, n_ranges, max_candidates, out);
+}
+
+extern "C" int dbeel_gpu_reader_scan_snapshot(
+    dbeel_gpu_reader* rd, const uint8_t* start_key, size_t start_key_len,
+    const uint8_t* end_key, size_t end_key_len, const uint32_t* range_starts,
+    const uint32_t* range_ends, size_t n_ranges, uint64_t max_candidates,
+    uint32_t flags, dbeel_gpu_reader_scan** out) {
+    g_err[0] = 0;
+    if (out) *out = nullptr;
+    if (flags & ~(uint32_t)(DBEEL_SCAN_MEMTABLE | DBEEL_SCAN_NEWEST_ONLY)) {
+        set_err("reader_scan_snapshot: unknown flags 0x%x (defined: "
+                "DBEEL_SCAN_MEMTABLE, DBEEL_SCAN_NEWEST_ONLY)", flags);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    return scan_begin_impl("reader_scan_snapshot", true, flags, rd, start_key,
+                           start_key_len, end_key, end_key_len, range_starts,
+                           range_ends, n_ranges, max_candidates, out);
 }
 
 static inline uint64_t scan_align16(uint64_t v) { return (v + 15) & ~15ull; }
@@ -5331,18 +5753,51 @@ extern "C" int dbeel_gpu_reader_scan_next(dbeel_gpu_reader_scan* sc,
         return DBEEL_ERR_INVALID_ARG;
     }
     dbeel_gpu_reader* rd = sc->rd;
-    if (sc->generation != rd->generation) {
+    if (!sc->snapshot && sc->generation != rd->generation) {
         set_err("reader_scan_next: stale scan (the table list changed since "
                 "scan_begin; start a new scan)");
         return DBEEL_ERR_INVALID_ARG;
     }
-    uint64_t m = sc->total - sc->cursor;
+    /* a page is cut from ONE descriptor: the tables' (at most 64 runs), or
+     * — once they are exhausted — the memtable segment's, a list of one.
+     * The page that exhausts the tables may therefore be short. */
+    const bool mem_page = sc->cursor >= sc->table_total;
+    uint64_t m = (mem_page ? sc->total : sc->table_total) - sc->cursor;
     if (m > sc->max_candidates) m = sc->max_candidates;
     if (m == 0) {
         page->done = 1;
         return DBEEL_OK;
     }
-    const RunsDesc& D = rd->desc;
+    RunsDesc mem_desc;
+    ScanWin mem_win;
+    if (mem_page) {
+        memset(&mem_desc, 0, sizeof mem_desc);
+        mem_desc.n_runs = 1;
+        mem_desc.total = sc->mem.count;
+        mem_desc.data[0] = sc->mem.data;
+        mem_desc.index[0] = sc->mem.index;
+        mem_desc.data_len[0] = sc->mem_data_len;
+        mem_desc.count[0] = sc->mem.count;
+        mem_desc.job_hi[0] = 1;
+        memset(&mem_win, 0, sizeof mem_win);
+        mem_win.cend[0] = sc->total - sc->table_total;
+        mem_win.adj[0] = sc->mem_lo;
+    }
+    const RunsDesc& D =
+        mem_page ? mem_desc : (sc->snapshot ? sc->desc : rd->desc);
+    const ScanWin& W = mem_page ? mem_win : sc->win;
+    const uint64_t c0 = mem_page ? sc->cursor - sc->table_total : sc->cursor;
+    /* nothing follows the memtable: its pages skip the shadow pass */
+    const bool shadow =
+        !mem_page && sc->snapshot && (sc->flags & DBEEL_SCAN_NEWEST_ONLY);
+    bool shadow_narrow = false;
+    if (shadow) {
+        /* read on every call, as DBEEL_BATCH_ORDER is; "full" is the
+         * default: the narrowed pass measured level with it (DESIGN.md
+         * §4b-7) */
+        const char* v = getenv("DBEEL_SCAN_SHADOW");
+        if (v && !strcmp(v, "narrow")) shadow_narrow = true;
+    }
     uint64_t resident = 0; /* no page can hold more than the tables do */
     for (int r = 0; r < D.n_runs; r++) resident += D.data_len[r];
     const uint64_t cap = data_cap < resident ? (uint64_t)data_cap : resident;
@@ -5385,9 +5840,19 @@ extern "C" int dbeel_gpu_reader_scan_next(dbeel_gpu_reader_scan* sc,
 
     HIP_CHECK(hipEventRecord(rd->ev[0], s));
     hipLaunchKernelGGL(k_reader_scan_flag, dim3(pick_grid(m, 256)), dim3(256),
-                       0, s, D, sc->win, sc->cursor, m, sc->d_ranges,
+                       0, s, D, W, c0, m, sc->d_ranges,
                        sc->d_ranges + sc->n_ranges, sc->n_ranges, d_rrec,
                        d_rid);
+    if (shadow) {
+        const uint32_t tiles =
+            (uint32_t)((m + SHADOW_BLOCK - 1) / SHADOW_BLOCK);
+        hipLaunchKernelGGL(shadow_narrow ? k_reader_scan_shadow<true>
+                                         : k_reader_scan_shadow<false>,
+                           dim3(tiles < 65535u * 16 ? tiles : 65535u * 16),
+                           dim3(SHADOW_BLOCK), 0, s, D, sc->pfx, sc->mem,
+                           sc->d_blooms, m, d_rrec);
+        HIP_CHECK(hipMemsetAsync(&rd->d_scantot->shadowed, 0, 8, s));
+    }
     HIP_CHECK(hipEventRecord(rd->ev[1], s));
     HIP_CHECK(survivor_scans(rd->d_scantmp, tmp_bytes, d_rrec, d_dst, d_pos,
                              m, s));
@@ -5395,6 +5860,10 @@ extern "C" int dbeel_gpu_reader_scan_next(dbeel_gpu_reader_scan* sc,
                        0, s, D, d_rrec, d_rid, d_dst, d_pos, m,
                        (uint64_t)data_cap, max_entries, d_oidx, d_smap,
                        d_rido, rd->d_scantot);
+    if (shadow)
+        hipLaunchKernelGGL(k_reader_scan_shadow_count,
+                           dim3(pick_grid(m, 256)), dim3(256), 0, s, d_rrec,
+                           d_rid, sc->n_ranges, rd->d_scantot);
     HIP_CHECK(hipEventRecord(rd->ev[2], s));
     {
         /* the copy's grid comes from an upper bound on the page's bytes,
@@ -5442,6 +5911,7 @@ extern "C" int dbeel_gpu_reader_scan_next(dbeel_gpu_reader_scan* sc,
     for (int i = 0; i < 5; i++)
         HIP_CHECK(hipEventElapsedTime(&ms[i], rd->ev[i], rd->ev[i + 1]));
     sc->cursor += next;
+    if (shadow) sc->shadowed += rd->h_scantot->shadowed;
     page->data_len = bytes;
     page->n_entries = taken;
     page->candidates = next;

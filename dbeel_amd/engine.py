@@ -578,6 +578,15 @@ def _load_reader() -> ctypes.CDLL:
         ]
         lib.dbeel_gpu_reader_scan_end.restype = None
         lib.dbeel_gpu_reader_scan_end.argtypes = [ctypes.c_void_p]
+        lib.dbeel_gpu_reader_scan_snapshot.restype = ctypes.c_int
+        lib.dbeel_gpu_reader_scan_snapshot.argtypes = (
+            lib.dbeel_gpu_reader_scan_begin.argtypes[:-1]
+            + [ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)])
+        lib.dbeel_gpu_reader_scan_info.restype = ctypes.c_int
+        lib.dbeel_gpu_reader_scan_info.argtypes = [
+            ctypes.c_void_p, ctypes.POINTER(ScanSnapshotInfo)]
+        lib.dbeel_gpu_reader_held_bytes.restype = ctypes.c_uint64
+        lib.dbeel_gpu_reader_held_bytes.argtypes = [ctypes.c_void_p]
         lib.dbeel_gpu_reader_write_batch.restype = ctypes.c_int
         lib.dbeel_gpu_reader_write_batch.argtypes = (
             [ctypes.c_void_p, ctypes.c_size_t] + _BATCH_ARGTYPES + [
@@ -625,13 +634,32 @@ class ScanPage(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+SCAN_MEMTABLE = 1      # DBEEL_SCAN_MEMTABLE
+SCAN_NEWEST_ONLY = 2   # DBEEL_SCAN_NEWEST_ONLY
+
+
+class ScanSnapshotInfo(ctypes.Structure):
+    """dbeel_scan_snapshot_info."""
+    _fields_ = [
+        ("n_tables", ctypes.c_uint32),
+        ("has_memtable", ctypes.c_uint32),
+        ("table_candidates", ctypes.c_uint64),
+        ("memtable_candidates", ctypes.c_uint64),
+        ("shadowed", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class ReaderScan:
     """One open paged scan of a Reader (dbeel_gpu_reader_scan_*): next()
     fills caller-owned numpy buffers with the next page. Made by
-    Reader.scan_open(); ended by close(), or by closing the reader."""
+    Reader.scan_open() or, with snapshot_flags (an int, 0 included), by
+    Reader.snapshot_open(); ended by close(), or by closing the reader."""
 
     def __init__(self, reader: "Reader", start_key, end_key, hash_ranges,
-                 max_candidates: int):
+                 max_candidates: int, snapshot_flags: int | None = None):
         if not reader._h:
             raise ValueError("reader is closed")
         self._reader = reader
@@ -654,9 +682,14 @@ class ReaderScan:
             rsp = rs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
             rep = re_.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
         h = ctypes.c_void_p()
-        rc = self._lib.dbeel_gpu_reader_scan_begin(
-            reader._h, sp, sl, ep, el, rsp, rep, self.n_ranges,
-            int(max_candidates), ctypes.byref(h))
+        if snapshot_flags is None:
+            rc = self._lib.dbeel_gpu_reader_scan_begin(
+                reader._h, sp, sl, ep, el, rsp, rep, self.n_ranges,
+                int(max_candidates), ctypes.byref(h))
+        else:
+            rc = self._lib.dbeel_gpu_reader_scan_snapshot(
+                reader._h, sp, sl, ep, el, rsp, rep, self.n_ranges,
+                int(max_candidates), int(snapshot_flags), ctypes.byref(h))
         del sa, ea  # begin has copied the bounds and ranges to the device
         if rc != 0:
             raise DbeelGpuError(rc, self._lib.dbeel_gpu_last_error().decode())
@@ -684,6 +717,17 @@ class ReaderScan:
             err.page = pg.as_dict()
             raise err
         return pg.as_dict()
+
+    def info(self) -> dict:
+        """dbeel_scan_snapshot_info as a dict: the snapshot's segments and
+        candidates, and the entries NEWEST_ONLY has dropped so far."""
+        if not self._h:
+            raise ValueError("scan is closed")
+        si = ScanSnapshotInfo()
+        rc = self._lib.dbeel_gpu_reader_scan_info(self._h, ctypes.byref(si))
+        if rc != 0:
+            raise DbeelGpuError(rc, self._lib.dbeel_gpu_last_error().decode())
+        return si.as_dict()
 
     def close(self):
         if self._h:
@@ -751,6 +795,12 @@ class Reader:
         """Device bytes held between calls, summed over the tables: run
         bytes + prefixes + bitmaps."""
         return int(self._lib.dbeel_gpu_reader_table_bytes(self._h))
+
+    @property
+    def held_bytes(self) -> int:
+        """Device bytes that left the list or the memtable's pair and live
+        only because a snapshot scan still reads them, each buffer once."""
+        return int(self._lib.dbeel_gpu_reader_held_bytes(self._h))
 
     @property
     def n_runs(self) -> int:
@@ -1004,6 +1054,41 @@ class Reader:
         return ReaderScan(self, start_key, end_key, hash_ranges,
                           max_candidates)
 
+    def snapshot_open(self, start_key=None, end_key=None, hash_ranges=None,
+                      max_candidates: int = 0, memtable: bool = False,
+                      newest_only: bool = False) -> ReaderScan:
+        """Begin a snapshot scan (dbeel_gpu_reader_scan_snapshot): nothing
+        done to the reader afterwards changes what it yields or makes it
+        stale. memtable=True appends the memtable of this moment as the last
+        segment; newest_only=True drops every entry whose key a later
+        segment of the snapshot holds. .info() reports its segments."""
+        flags = ((SCAN_MEMTABLE if memtable else 0)
+                 | (SCAN_NEWEST_ONLY if newest_only else 0))
+        return ReaderScan(self, start_key, end_key, hash_ranges,
+                          max_candidates, snapshot_flags=flags)
+
+    def snapshot_pages(self, start_key=None, end_key=None, hash_ranges=None,
+                       page_bytes: int = 64 << 20,
+                       page_entries: int = 1 << 20, max_candidates: int = 0,
+                       pinned: bool = False, memtable: bool = False,
+                       newest_only: bool = False):
+        """scan_pages over a snapshot scan (see snapshot_open)."""
+        return self._pages(
+            lambda: self.snapshot_open(start_key, end_key, hash_ranges,
+                                       max_candidates, memtable, newest_only),
+            bool(hash_ranges), page_bytes, page_entries, pinned)
+
+    def snapshot(self, start_key=None, end_key=None, hash_ranges=None,
+                 page_bytes: int = 64 << 20, page_entries: int = 1 << 20,
+                 max_candidates: int = 0, pinned: bool = False,
+                 return_range_ids: bool = False, memtable: bool = False,
+                 newest_only: bool = False):
+        """scan over a snapshot scan (see snapshot_open)."""
+        return self._joined(
+            self.snapshot_pages(start_key, end_key, hash_ranges, page_bytes,
+                                page_entries, max_candidates, pinned,
+                                memtable, newest_only), return_range_ids)
+
     def scan_pages(self, start_key=None, end_key=None, hash_ranges=None,
                    page_bytes: int = 64 << 20, page_entries: int = 1 << 20,
                    max_candidates: int = 0, pinned: bool = False):
@@ -1017,10 +1102,18 @@ class Reader:
         engine.scan's; the pages concatenated are its result. pinned=True
         page-locks the buffers for the scan's lifetime. An entry larger
         than page_bytes raises DbeelGpuError (code 3, .page["needed"])."""
+        return self._pages(
+            lambda: self.scan_open(start_key, end_key, hash_ranges,
+                                   max_candidates),
+            bool(hash_ranges), page_bytes, page_entries, pinned)
+
+    def _pages(self, opener, ranged: bool, page_bytes: int,
+               page_entries: int, pinned: bool):
+        """The page loop of scan_pages / snapshot_pages over opener()'s
+        scan."""
         data = np.empty(page_bytes, dtype=np.uint8)
         index = np.empty(page_entries * 16, dtype=np.uint8)
-        rid = (np.empty(page_entries, dtype=np.uint32)
-               if hash_ranges else None)
+        rid = np.empty(page_entries, dtype=np.uint32) if ranged else None
         bufs = [b for b in (data, index, rid) if b is not None]
         done_pin = []
         sc = None
@@ -1029,8 +1122,7 @@ class Reader:
                 for b in bufs:
                     pin_host(b)
                     done_pin.append(b)
-            sc = self.scan_open(start_key, end_key, hash_ranges,
-                                max_candidates)
+            sc = opener()
             while True:
                 pg = sc.next(data, index, rid)
                 n = pg["n_entries"]
@@ -1051,12 +1143,18 @@ class Reader:
         """engine.scan over the resident runs: (data_bytes, index_bytes, n)
         with the pages' index offsets rebased into one run file; with
         return_range_ids also the u32 array of first matching ranges."""
+        return self._joined(
+            self.scan_pages(start_key, end_key, hash_ranges, page_bytes,
+                            page_entries, max_candidates, pinned),
+            return_range_ids)
+
+    @staticmethod
+    def _joined(pages, return_range_ids: bool):
+        """Concatenates pages into one run file (offsets rebased)."""
         datas, indexes, rids = [], [], []
         off = 0
         total = 0
-        for d, x, n, rid in self.scan_pages(
-                start_key, end_key, hash_ranges, page_bytes, page_entries,
-                max_candidates, pinned):
+        for d, x, n, rid in pages:
             if not n:
                 continue
             rec = x.view(INDEX_DTYPE).copy()

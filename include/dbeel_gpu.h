@@ -323,7 +323,8 @@ void dbeel_gpu_reader_compact_abort(dbeel_gpu_reader* reader);
  * compact_commit change the list and invalidate every open scan: next then returns DBEEL_ERR_INVALID_ARG
  * ("stale scan") and the caller restarts; compact_begin / compact_abort do
  * not. (Divergence: the reference's iterator keeps its cloned list alive,
- * lsm_tree.rs:175-177.) Any number of scans may be open on a reader, under
+ * lsm_tree.rs:175-177; dbeel_gpu_reader_scan_snapshot below does the
+ * same.) Any number of scans may be open on a reader, under
  * the same one-thread-per-reader contract; dbeel_gpu_reader_close ends the
  * scans still open, after which their handles must not be used. */
 typedef struct dbeel_gpu_reader_scan dbeel_gpu_reader_scan;
@@ -336,8 +337,9 @@ typedef struct {
                               entry that did not fit; else 0                */
     int      done;         /* 1 = nothing left after this page              */
     double   flag_ms, emit_ms, copy_ms, d2h_ms; /* HIP events, reader stream:
-                              flag kernel | scans + emit | winmap + copy |
-                              copies into the caller's buffers             */
+                              flag kernel (and, under DBEEL_SCAN_NEWEST_ONLY,
+                              the shadow pass) | scans + emit | winmap +
+                              copy | copies into the caller's buffers      */
 } dbeel_scan_page;
 
 int  dbeel_gpu_reader_scan_begin(dbeel_gpu_reader* reader,
@@ -354,6 +356,96 @@ int  dbeel_gpu_reader_scan_next(dbeel_gpu_reader_scan* scan,
         dbeel_scan_page* page);
 /* Frees the scan; NULL is a no-op. */
 void dbeel_gpu_reader_scan_end(dbeel_gpu_reader_scan* scan);
+
+/* ---- Snapshot scans: the memtable as last segment, no stale scans,
+ * shadowed versions dropped on the device ----
+ * The reference's AsyncIter clones the sstable list — "the sstable files we
+ * operate on will not be deleted until this object is dropped"
+ * (lsm_tree.rs:175-177) — and yields the sstables and then the memtable
+ * (lsm_tree.rs:155-173, 279). scan_snapshot opens a scan that does both;
+ * pages are drawn with dbeel_gpu_reader_scan_next and the scan is ended with
+ * dbeel_gpu_reader_scan_end, and dbeel_gpu_reader_scan_begin's filters, hash
+ * function, between_cmp wrapped case, range_ids, ITEM_TOO_LARGE protocol and
+ * page shape apply unchanged.
+ *
+ * Segments: the tables at positions 0 .. n_runs-1 as the list stands at the
+ * call (a pending compaction output is invisible, as for gets) and, with
+ * DBEEL_SCAN_MEMTABLE and a non-empty memtable, the memtable as it stands at
+ * the call as the LAST segment, its key-range bounds bisected on its own
+ * prefix array. Yield order: segment ascending, key order within a segment.
+ * With flags == 0 the pages concatenated are byte-identical to the old
+ * scan's; with an empty memtable DBEEL_SCAN_MEMTABLE changes nothing. A page
+ * never mixes table entries with memtable entries (64 tables plus the
+ * memtable are 65 segments, one more than a descriptor holds): the page that
+ * exhausts the tables may be short, the next one starts the memtable
+ * segment, and done is set only when both are exhausted. The concatenation
+ * stays independent of caps and max_candidates.
+ *
+ * Snapshot: nothing done to the reader afterwards — insert_run, write_batch,
+ * compact_begin / commit / abort, put, memtable_flush, memtable_clear —
+ * changes what the scan yields or makes it stale; the remaining pages are
+ * those that would have followed had they been drawn at once.
+ * dbeel_gpu_reader_close still ends every open scan.
+ *
+ * Ownership: a table's device buffers are reference-counted — one reference
+ * for the list, one per snapshot scan; compact_commit drops the list's and
+ * the last holder frees. The memtable buffer a snapshot reads is held the
+ * same way: a put about to write into a held buffer of the ping-pong pair
+ * hands it over to its holders and takes a fresh one for the pair. The call
+ * copies nothing whose size depends on the memtable. table_bytes counts the
+ * list (plus pending) and memtable_info.reserved_bytes the pair, as before;
+ * dbeel_gpu_reader_held_bytes counts the device bytes that belong to neither
+ * any more and live only because a scan holds them, each buffer once: 0
+ * right after the call, 0 again when the holding scans have ended. A failed
+ * call leaves the reader, its memtable, its scans and all three counts as
+ * they were.
+ *
+ * DBEEL_SCAN_NEWEST_ONLY: an entry of segment s is dropped when a segment
+ * t > s OF THE SNAPSHOT holds a byte-equal key (a tombstone shadows like any
+ * entry and is itself emitted when it is the last version; without
+ * DBEEL_SCAN_MEMTABLE the memtable neither appears nor shadows). The
+ * receiver applies entries in arrival order through a set() that replaces
+ * whatever the timestamps are (rbtree_arena/src/lib.rs:497-511,
+ * tasks/migration.rs:62-131), so its final state is unchanged. The result
+ * equals filtering first and then keeping, per key, the entry of the highest
+ * segment. The shadowing entry is looked for in the whole later segment,
+ * wherever the page windows fall. A dropped entry counts in
+ * page->candidates and in info.shadowed. flag_ms of a page INCLUDES the
+ * shadow pass. The pass has two variants with the same result, chosen by
+ * DBEEL_SCAN_SHADOW in the environment, read on every next: "full" (the
+ * default) bisects each whole later segment per candidate; "narrow"
+ * bisects, per block of 256 consecutive candidates, only the slice of each
+ * later segment the block's keys can fall into. The two measured level on
+ * cfg3, so the plainer one is the default.
+ *
+ * Validated on the host before any device call, in this order: flag bits
+ * other than the two defined (DBEEL_ERR_INVALID_ARG, the message names the
+ * flags); then dbeel_gpu_reader_scan_begin's checks in its order.
+ *
+ * scan_info works on either kind of scan; one opened by scan_begin reports
+ * n_tables, table_candidates and zeros elsewhere. A NULL scan or info is
+ * DBEEL_ERR_INVALID_ARG. held_bytes(NULL) is 0. */
+#define DBEEL_SCAN_MEMTABLE     1u  /* the memtable is the last segment      */
+#define DBEEL_SCAN_NEWEST_ONLY  2u  /* drop entries shadowed by a later one  */
+
+typedef struct {
+    uint32_t n_tables;            /* tables in the snapshot                       */
+    uint32_t has_memtable;        /* 1 = a non-empty memtable segment is included */
+    uint64_t table_candidates;    /* in-key-range entries, tables                 */
+    uint64_t memtable_candidates; /* in-key-range entries, memtable segment       */
+    uint64_t shadowed;            /* entries dropped by NEWEST_ONLY so far        */
+} dbeel_scan_snapshot_info;
+
+int dbeel_gpu_reader_scan_snapshot(dbeel_gpu_reader* reader,
+        const uint8_t* start_key, size_t start_key_len,
+        const uint8_t* end_key,   size_t end_key_len,
+        const uint32_t* range_starts, const uint32_t* range_ends,
+        size_t n_ranges,
+        uint64_t max_candidates /* per page; 0 = default 2^20 */,
+        uint32_t flags, dbeel_gpu_reader_scan** out);
+int dbeel_gpu_reader_scan_info(const dbeel_gpu_reader_scan* scan,
+                               dbeel_scan_snapshot_info* info);
+uint64_t dbeel_gpu_reader_held_bytes(const dbeel_gpu_reader* reader);
 
 /* ---- Run encoder (the memtable-flush path) ----
  * Encodes an already-sorted (key, value, timestamp) stream into a run:
@@ -470,7 +562,8 @@ int dbeel_gpu_flush_batch(uint64_t n_writes, const uint8_t* keys,
  * Liveness: a put does not edit the table list and bumps no generation, so
  * open scans stay valid. Scans do NOT see the memtable (documented
  * divergence from lsm_tree.rs:155-173: the caller flushes before
- * migrating). A non-empty flush is a list edit at the end: open scans go
+ * migrating, or opens the scan with dbeel_gpu_reader_scan_snapshot and
+ * DBEEL_SCAN_MEMTABLE). A non-empty flush is a list edit at the end: open scans go
  * stale, a pending compaction's positions do not move. A reader at 64
  * tables still takes puts and answers from them (hit.run == 64);
  * memtable_flush on it is DBEEL_ERR_INVALID_ARG and keeps the memtable. On

@@ -6,8 +6,9 @@ scans begin + next + end, one left for close to end / insert / compact
 begin + abort + commit / write batches with fetch on and off, a filter,
 both order paths and a refused call / memtable put x N + get + fetch +
 flush + clear, with the storage pair checked never to shrink nor to regrow
-after a flush / close with a non-empty memtable), reporting hipMemGetInfo
-drift. A leak in any path shows as monotonically shrinking free memory.
+after a flush / snapshot scans begun, paged and ended across an insert, two
+puts and a compaction, one left for close / close with a non-empty
+memtable), reporting hipMemGetInfo drift. A leak in any path shows as monotonically shrinking free memory.
 
     python tools/leakcheck.py --iters 40
 """
@@ -157,7 +158,33 @@ def main():
                 rd.put(batch[::2])
                 if rd.memtable_info["reserved_bytes"] != reserved:
                     raise SystemExit("memtable storage regrew after a flush")
-                rd.get(probe_keys[:1000])  # close frees the memtable
+                rd.get(probe_keys[:1000])
+                # snapshot scans: begin, edit the list and the memtable
+                # under them, page, end — what the list and the pair let go
+                # of is freed by the last scan's end, or by close for the
+                # one left open
+                page = (np.empty(1 << 20, dtype=np.uint8),
+                        np.empty(16 * 4096, dtype=np.uint8))
+                snaps = [rd.snapshot_open(memtable=True, newest_only=True,
+                                          max_candidates=4096),
+                         rd.snapshot_open(memtable=True),
+                         rd.snapshot_open(end_key=b"\x80", memtable=True)]
+                snaps[0].next(*page)
+                rd.compact_abort()  # the one pending from above
+                rd.insert_run(0, runs2[1])
+                rd.put(batch[:2000])
+                rd.put(batch[2000:4000])  # displaces the held buffer
+                rd.compact([1, 2], 1, True, fetch=False)
+                if not rd.held_bytes:
+                    raise SystemExit("nothing held after compact + puts")
+                for sc in snaps[:2]:
+                    while not sc.next(*page)["done"]:
+                        pass
+                    sc.close()
+                if not rd.held_bytes:
+                    raise SystemExit("the open snapshot holds nothing")
+                rd.compact_begin([0, 1], True, fetch=False)
+                # close aborts that, ends snaps[2] and frees the memtable
             flush_batch(batch[:7000], device=0)
             f = free_mem()
             if base is None:
