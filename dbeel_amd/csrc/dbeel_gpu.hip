@@ -2650,7 +2650,10 @@ extern "C" int dbeel_gpu_lookup(const dbeel_run_view* runs, size_t n_runs,
 /*                      the tables, in an instantiation of its own.   */
 /*   rocPRIM scan     : value_len -> exclusive value offsets.         */
 /*   k_reader_gather  : wave per hit, 8-B chunks, exact-length reads. */
-/*   k_reader_adopt   : a compaction output copied device-to-device   */
+/*   k_reader_gather_entries : get_entries' gather (further down):    */
+/*                      data_len | data | timestamp per hit,          */
+/*                      tombstones included.                          */
+/*   k_reader_adopt  : a compaction output copied device-to-device   */
 /*                      into a new table gets its prefixes and filter */
 /*                      bits in one pass (no validation: the engine   */
 /*                      just wrote it).                               */
@@ -4853,6 +4856,253 @@ extern "C" int dbeel_gpu_reader_get(dbeel_gpu_reader* rd,
         stats->hits = hstats[RS_HITS];
         stats->tombstones = hstats[RS_TOMBS];
     }
+    fail.dismiss();
+    return DBEEL_OK;
+}
+
+/* ------------------------------------------------------------------ */
+/* get_entries: LSMTree::get_entry's answer (lsm_tree.rs:674-723),    */
+/* EntryValue { data, timestamp }, into caller buffers                */
+/*                                                                    */
+/* A stored entry ends in data_len:u64 | data | timestamp:i128, which */
+/* is the bincode form of EntryValue: the record of a hit is those    */
+/* 24 + value_len bytes, copied verbatim. The search is reader_get's  */
+/* kernel, launched the same way; only what follows it differs.       */
+/* ------------------------------------------------------------------ */
+
+/* Record size of a hit. A found tombstone is a 24-B record, so the zeroed
+ * sentinel reader_get appends (run 0, value_len 0) would count here: this
+ * path's sentinel is run = -1. */
+struct HitRecordLen {
+    __device__ uint64_t operator()(const dbeel_lookup_hit& h) const {
+        return h.run < 0 ? 0 : h.value_len + 24;
+    }
+};
+
+/* One wave per delivered query copies data_len | data | timestamp, the
+ * entry's bytes from value_offset - 8 to its end, reading exactly the record
+ * and writing exactly the record. Tombstones are copied like any hit. The
+ * bounds are those validated at open (off + full_size <= data_len). */
+__global__ void k_reader_gather_entries(RunsDesc R, const uint8_t* mem_data,
+                                        const dbeel_lookup_hit* hits,
+                                        const uint64_t* rec_off,
+                                        uint64_t n_done, uint8_t* records) {
+    uint32_t lane = threadIdx.x & 63;
+    uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    for (uint64_t q = wave; q < n_done; q += n_waves) {
+        const dbeel_lookup_hit h = hits[q];
+        if (h.run < 0) continue;
+        /* run == n_runs names the memtable; with 64 tables that index lies
+         * past R's arrays, so it is resolved before any of them is read */
+        const uint8_t* src = h.run >= R.n_runs ? mem_data : R.data[h.run];
+        wave_copy_bytes(records + rec_off[q], src + h.value_offset - 8,
+                        h.value_len + 24, lane);
+    }
+}
+
+extern "C" int dbeel_gpu_reader_get_entries(
+    dbeel_gpu_reader* rd, const uint8_t* keys, const uint64_t* key_offsets,
+    uint64_t n_keys, const dbeel_get_buffers* buf, dbeel_get_page* page,
+    dbeel_get_stats* stats) {
+    g_err[0] = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (page) memset(page, 0, sizeof *page);
+    if (!rd || !buf || !page) {
+        set_err("reader_get_entries: null reader, buf or page");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (n_keys &&
+        (!keys || !key_offsets || !buf->hits || !buf->record_offsets)) {
+        set_err("reader_get_entries: null keys, key_offsets, hits or "
+                "record_offsets");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (!buf->records && buf->records_cap) {
+        set_err("reader_get_entries: null records with records_cap %llu",
+                (unsigned long long)buf->records_cap);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (n_keys >= (1ull << 32)) {
+        set_err("reader_get_entries: 2^32 or more keys in one batch");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    for (uint64_t i = 0; i < n_keys; i++)
+        if (key_offsets[i + 1] < key_offsets[i]) {
+            set_err("reader_get_entries: key_offsets not ascending at %llu",
+                    (unsigned long long)i);
+            return DBEEL_ERR_INVALID_ARG;
+        }
+    const uint64_t n = n_keys;
+    if (n == 0) {
+        if (buf->record_offsets) buf->record_offsets[0] = 0;
+        return DBEEL_OK;
+    }
+
+    const uint64_t kbytes = key_offsets[n];
+    /* d_batch layout: key offsets (n+1) | record offsets (n+1) | hits (n+1,
+     * the last one absent so the scan's final element is the total) */
+    const uint64_t off_bytes = (n + 1) * sizeof(uint64_t);
+    size_t tmp_bytes = 0;
+    unsigned long long hstats[RS_N] = {};
+    float ms[6] = {};
+    hipStream_t s = rd->stream;
+    /* on failure nothing of this batch may still be in flight into the
+     * caller's buffers */
+    ScopeGuard fail([&] { (void)hipStreamSynchronize(s); });
+
+    HIP_CHECK(hipSetDevice(rd->device));
+    HIP_CHECK(reader_reserve((void**)&rd->d_keys, &rd->keys_cap,
+                             kbytes ? kbytes : 1));
+    HIP_CHECK(reader_reserve((void**)&rd->d_batch, &rd->batch_cap,
+                             2 * off_bytes +
+                                 (n + 1) * sizeof(dbeel_lookup_hit)));
+    uint64_t* d_koff = (uint64_t*)rd->d_batch;
+    uint64_t* d_roff = d_koff + (n + 1);
+    dbeel_lookup_hit* d_hits = (dbeel_lookup_hit*)(d_roff + (n + 1));
+    HIP_CHECK(rocprim::exclusive_scan(
+        nullptr, tmp_bytes,
+        rocprim::make_transform_iterator(d_hits, HitRecordLen{}), d_roff,
+        (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), s));
+    HIP_CHECK(reader_reserve(&rd->d_scantmp, &rd->scantmp_cap,
+                             tmp_bytes ? tmp_bytes : 1));
+
+    HIP_CHECK(hipEventRecord(rd->ev[0], s));
+    if (kbytes)
+        HIP_CHECK(hipMemcpyAsync(rd->d_keys, keys, kbytes,
+                                 hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_koff, key_offsets, off_bytes,
+                             hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemsetAsync(rd->d_stats, 0, RS_N * sizeof(uint64_t), s));
+    /* all-ones bytes: run = -1 */
+    HIP_CHECK(hipMemsetAsync(d_hits + n, 0xFF, sizeof(dbeel_lookup_hit), s));
+    HIP_CHECK(hipEventRecord(rd->ev[1], s));
+    void (*ks)(RunsDesc, ReaderPfx, ReaderMem, const ReaderBloom*,
+               const uint8_t*, const uint64_t*, uint64_t, dbeel_lookup_hit*,
+               unsigned long long*) = k_reader_search<false>;
+    if (rd->mem.count) ks = k_reader_search<true>;
+    hipLaunchKernelGGL(ks, dim3(pick_grid(n, READER_BLOCK)),
+                       dim3(READER_BLOCK),
+                       0, s, rd->desc, rd->pfx, rd->mem.view(), rd->d_blooms,
+                       rd->d_keys, d_koff, n, d_hits, rd->d_stats);
+    HIP_CHECK(hipEventRecord(rd->ev[2], s));
+    HIP_CHECK(rocprim::exclusive_scan(
+        rd->d_scantmp, tmp_bytes,
+        rocprim::make_transform_iterator(d_hits, HitRecordLen{}), d_roff,
+        (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), s));
+    HIP_CHECK(hipEventRecord(rd->ev[3], s));
+    /* hits and offsets go out complete whatever the cap; the offsets are
+     * what the host sizes the page from */
+    HIP_CHECK(hipMemcpyAsync(buf->record_offsets, d_roff, off_bytes,
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(buf->hits, d_hits, n * sizeof *buf->hits,
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(hstats, rd->d_stats, sizeof hstats,
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipEventRecord(rd->ev[4], s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipGetLastError());
+    for (int i = 0; i < 4; i++)
+        HIP_CHECK(hipEventElapsedTime(&ms[i], rd->ev[i], rd->ev[i + 1]));
+
+    /* n_done = the largest d with record_offsets[d] <= records_cap, by
+     * bisection over the ascending offsets (offsets[0] = 0 always fits) */
+    const uint64_t* off = buf->record_offsets;
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo + 1) / 2;
+        if (off[mid] <= buf->records_cap)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    const uint64_t n_done = lo, len = off[n_done];
+    page->n_done = n_done;
+    page->records_len = len;
+    page->records_total = off[n];
+    /* record n_done did not fit, so it is not empty */
+    page->needed = n_done < n ? off[n_done + 1] - off[n_done] : 0;
+
+    if (len) {
+        HIP_CHECK(reader_reserve((void**)&rd->d_values, &rd->values_cap,
+                                 len));
+        HIP_CHECK(hipEventRecord(rd->ev[4], s));
+        hipLaunchKernelGGL(k_reader_gather_entries,
+                           dim3(pick_grid(n_done * 64, 256)), dim3(256), 0, s,
+                           rd->desc, rd->mem.view().data, d_hits, d_roff,
+                           n_done, rd->d_values);
+        HIP_CHECK(hipEventRecord(rd->ev[5], s));
+        HIP_CHECK(hipMemcpyAsync(buf->records, rd->d_values, len,
+                                 hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipEventRecord(rd->ev[6], s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventElapsedTime(&ms[4], rd->ev[4], rd->ev[5]));
+        HIP_CHECK(hipEventElapsedTime(&ms[5], rd->ev[5], rd->ev[6]));
+    }
+    if (stats) {
+        stats->h2d_ms = ms[0];
+        stats->search_ms = ms[1];
+        stats->gather_ms = ms[2] + ms[4]; /* offset scan + record gather */
+        stats->d2h_ms = ms[3] + ms[5];    /* every copy to the caller    */
+        stats->bloom_probes = hstats[RS_PROBES];
+        stats->bloom_skips = hstats[RS_SKIPS];
+        stats->searches = hstats[RS_SEARCHES];
+        stats->hits = hstats[RS_HITS];
+        stats->tombstones = hstats[RS_TOMBS];
+    }
+    fail.dismiss();
+    if (n_done == 0) { /* n > 0: record 0 alone is over the cap */
+        set_err("reader_get_entries: record 0 needs %llu bytes, "
+                "records_cap is %llu", (unsigned long long)page->needed,
+                (unsigned long long)buf->records_cap);
+        return DBEEL_ERR_ITEM_TOO_LARGE;
+    }
+    return DBEEL_OK;
+}
+
+extern "C" int dbeel_gpu_reader_compact_fetch(
+    dbeel_gpu_reader* rd, uint8_t* data, uint64_t data_cap, uint8_t* index,
+    uint64_t index_cap, uint64_t* data_len, uint64_t* index_len,
+    double* d2h_ms) {
+    g_err[0] = 0;
+    if (data_len) *data_len = 0;
+    if (index_len) *index_len = 0;
+    if (d2h_ms) *d2h_ms = 0;
+    if (!rd || !data || !index || !data_len || !index_len) {
+        set_err("reader_compact_fetch: null argument");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (!rd->has_pending) {
+        set_err("reader_compact_fetch: no compaction pending");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    const ReaderTable& t = rd->pending;
+    const uint64_t dl = t.data_len, il = t.count * 16;
+    *data_len = dl;
+    *index_len = il;
+    if (dl > data_cap || il > index_cap) {
+        set_err("reader_compact_fetch: output needs %llu data and %llu index "
+                "bytes, caps are %llu and %llu", (unsigned long long)dl,
+                (unsigned long long)il, (unsigned long long)data_cap,
+                (unsigned long long)index_cap);
+        return DBEEL_ERR_ITEM_TOO_LARGE;
+    }
+    hipStream_t s = rd->stream;
+    ScopeGuard fail([&] { (void)hipStreamSynchronize(s); });
+    HIP_CHECK(hipSetDevice(rd->device));
+    HIP_CHECK(hipEventRecord(rd->ev[0], s));
+    if (dl)
+        HIP_CHECK(hipMemcpyAsync(data, t.data(), dl, hipMemcpyDeviceToHost,
+                                 s));
+    if (il)
+        HIP_CHECK(hipMemcpyAsync(index, t.index(), il, hipMemcpyDeviceToHost,
+                                 s));
+    HIP_CHECK(hipEventRecord(rd->ev[1], s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, rd->ev[0], rd->ev[1]));
+    if (d2h_ms) *d2h_ms = ms;
     fail.dismiss();
     return DBEEL_OK;
 }

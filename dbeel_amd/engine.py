@@ -425,6 +425,29 @@ class GetStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class GetBuffers(ctypes.Structure):
+    """dbeel_get_buffers: all caller-owned."""
+    _fields_ = [
+        ("hits", ctypes.POINTER(LookupHit)),
+        ("record_offsets", ctypes.POINTER(ctypes.c_uint64)),
+        ("records", ctypes.POINTER(ctypes.c_uint8)),
+        ("records_cap", ctypes.c_uint64),
+    ]
+
+
+class GetPage(ctypes.Structure):
+    """dbeel_get_page."""
+    _fields_ = [
+        ("n_done", ctypes.c_uint64),
+        ("records_len", ctypes.c_uint64),
+        ("records_total", ctypes.c_uint64),
+        ("needed", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class ReaderCompactStats(ctypes.Structure):
     _fields_ = [
         ("pipeline", CompactTimings),
@@ -612,6 +635,15 @@ def _load_reader() -> ctypes.CDLL:
             ctypes.POINTER(_U8P), _U64P]
         lib.dbeel_gpu_reader_memtable_clear.restype = None
         lib.dbeel_gpu_reader_memtable_clear.argtypes = [ctypes.c_void_p]
+        lib.dbeel_gpu_reader_get_entries.restype = ctypes.c_int
+        lib.dbeel_gpu_reader_get_entries.argtypes = [
+            ctypes.c_void_p, _U8P, _U64P, ctypes.c_uint64,
+            ctypes.POINTER(GetBuffers), ctypes.POINTER(GetPage),
+            ctypes.POINTER(GetStats)]
+        lib.dbeel_gpu_reader_compact_fetch.restype = ctypes.c_int
+        lib.dbeel_gpu_reader_compact_fetch.argtypes = [
+            ctypes.c_void_p, _U8P, ctypes.c_uint64, _U8P, ctypes.c_uint64,
+            _U64P, _U64P, ctypes.POINTER(ctypes.c_double)]
         lib._reader_ready = True
     return lib
 
@@ -1046,6 +1078,128 @@ class Reader:
         off = voff.tolist()
         return [None if r < 0 else blob[off[q] : off[q + 1]]
                 for q, r in enumerate(hits["run"].tolist())]
+
+    def _get_entries_into(self, ka, koff, hits, roff, records, cap):
+        """dbeel_gpu_reader_get_entries over the key blob ka / offsets koff
+        (len(koff) - 1 keys) into the caller's arrays: hits (HIT_DTYPE, n),
+        roff (u64, n + 1), records (u8, at least cap bytes, or None with
+        cap 0). -> (rc, GetPage, GetStats); nothing is raised."""
+        if not self._h:
+            raise ValueError("reader is closed")
+        n = len(koff) - 1
+        buf = GetBuffers(
+            hits.ctypes.data_as(ctypes.POINTER(LookupHit)),
+            roff.ctypes.data_as(_U64P),
+            None if records is None else records.ctypes.data_as(_U8P),
+            cap)
+        page = GetPage()
+        st = GetStats()
+        rc = self._lib.dbeel_gpu_reader_get_entries(
+            self._h, ka.ctypes.data_as(_U8P), koff.ctypes.data_as(_U64P), n,
+            ctypes.byref(buf), ctypes.byref(page), ctypes.byref(st))
+        return rc, page, st
+
+    def get_entries_raw(self, keys, records=None, records_cap=None):
+        """get_entry for a batch, with timestamps: -> (hits HIT_DTYPE array,
+        record_offsets u64[n+1], records view, page dict, stats dict). The
+        record of a found key — a tombstone included — is the stored
+        `data_len:u64 | data | timestamp:i128`, 24 + value_len bytes, the
+        bincode form of EntryValue; an absent key has an empty range.
+        record_offsets covers ALL keys; the records of the first
+        page["n_done"] keys are in the view (records[:page["records_len"]]);
+        call again with keys[n_done:] for the rest.
+
+        records is a caller np.uint8 array (pin_host it for true async DMA),
+        of which records_cap bytes (default: all) may be written; when it is
+        omitted one of records_cap bytes (default 64 MiB) is allocated. If
+        the first record alone is over the cap, DbeelGpuError
+        (ITEM_TOO_LARGE) is raised carrying .page (needed = its size), .hits
+        and .record_offsets, which are complete."""
+        ka, koff = _key_blob(keys)
+        n = len(keys)
+        if records is None:
+            cap = (64 << 20) if records_cap is None else int(records_cap)
+            records = np.empty(max(cap, 1), dtype=np.uint8)
+        else:
+            if (records.dtype != np.uint8 or records.ndim != 1
+                    or not records.flags.c_contiguous):
+                raise ValueError("records must be a contiguous 1-D uint8 "
+                                 "array")
+            cap = records.size if records_cap is None else int(records_cap)
+            if cap > records.size:
+                raise ValueError("records_cap exceeds the records array")
+        hits = np.empty(n, dtype=HIT_DTYPE)
+        roff = np.zeros(n + 1, dtype=np.uint64)
+        rc, page, st = self._get_entries_into(ka, koff, hits, roff, records,
+                                              cap)
+        if rc != 0:
+            err = DbeelGpuError(rc, self._lib.dbeel_gpu_last_error().decode())
+            err.page, err.hits, err.record_offsets = page.as_dict(), hits, roff
+            raise err
+        return (hits, roff, records[:int(page.records_len)], page.as_dict(),
+                st.as_dict())
+
+    def get_entries(self, keys, page_bytes: int = 64 << 20):
+        """LSMTree::get_entry for a batch: a list of None (absent) or
+        (data: bytes, timestamp: int), a deleted key being (b"", ts) — what
+        a replicated read compares timestamps on before it tests for the
+        tombstone. Pages of page_bytes are drawn until every key is
+        answered; a record larger than the page grows the buffer to its
+        size, once."""
+        keys = list(keys)
+        records = np.empty(max(int(page_bytes), 1), dtype=np.uint8)
+        cap = int(page_bytes)
+        out = []
+        grown = False
+        while len(out) < len(keys):
+            try:
+                hits, roff, view, page, _ = self.get_entries_raw(
+                    keys[len(out):], records=records, records_cap=cap)
+            except DbeelGpuError as e:
+                if e.code != 3 or grown:
+                    raise
+                cap = int(e.page["needed"])
+                records = np.empty(cap, dtype=np.uint8)
+                grown = True
+                continue
+            grown = False
+            blob = view.tobytes()
+            off = roff.tolist()
+            for q, r in enumerate(hits["run"][:page["n_done"]].tolist()):
+                if r < 0:
+                    out.append(None)
+                    continue
+                rec = blob[off[q]:off[q + 1]]
+                out.append((rec[8:-16],
+                            int.from_bytes(rec[-16:], "little", signed=True)))
+        return out
+
+    def compact_fetch_into(self, data_arr, index_arr):
+        """Copy the PENDING compaction output's .data / .index bytes — what
+        compact_begin(fetch=True) returns — into the caller's np.uint8
+        arrays (pin_host them for true async DMA): -> (data_len, index_len,
+        d2h_ms). Use after compact_begin(fetch=False); callable any number
+        of times until commit / abort. An array too small raises
+        DbeelGpuError (ITEM_TOO_LARGE) carrying .data_len / .index_len, the
+        sizes needed; nothing is written and the pending table is kept."""
+        if not self._h:
+            raise ValueError("reader is closed")
+        for a in (data_arr, index_arr):
+            if (a.dtype != np.uint8 or a.ndim != 1
+                    or not a.flags.c_contiguous):
+                raise ValueError("buffers must be contiguous 1-D uint8 "
+                                 "arrays")
+        dl, il = ctypes.c_uint64(), ctypes.c_uint64()
+        ms = ctypes.c_double()
+        rc = self._lib.dbeel_gpu_reader_compact_fetch(
+            self._h, data_arr.ctypes.data_as(_U8P), data_arr.size,
+            index_arr.ctypes.data_as(_U8P), index_arr.size,
+            ctypes.byref(dl), ctypes.byref(il), ctypes.byref(ms))
+        if rc != 0:
+            err = DbeelGpuError(rc, self._lib.dbeel_gpu_last_error().decode())
+            err.data_len, err.index_len = int(dl.value), int(il.value)
+            raise err
+        return int(dl.value), int(il.value), float(ms.value)
 
     def scan_open(self, start_key=None, end_key=None, hash_ranges=None,
                   max_candidates: int = 0) -> ReaderScan:

@@ -211,6 +211,85 @@ void dbeel_gpu_get_result_free(dbeel_get_result* r);
 /* Frees the reader; a pending compaction is aborted, open scans are ended. */
 void dbeel_gpu_reader_close(dbeel_gpu_reader* reader);
 
+/* ---- get_entries: values WITH timestamps, into caller buffers ----
+ * LSMTree::get_entry (lsm_tree.rs:674-723) returns EntryValue { data,
+ * timestamp }: the replicated read takes max_by_key(timestamp) over the
+ * local and the remote answers and only then tests for a tombstone
+ * (tasks/db_server.rs:338-363), and a replica answers with
+ * ShardResponse::Get(Option<EntryValue>) in bincode
+ * (remote_shard_connection.rs:105-113). A stored entry is
+ * key_len | key | data_len | data | timestamp, so its bytes from data_len to
+ * its end ARE the bincode form of EntryValue; the record of a found key is
+ * that contiguous range, copied verbatim.
+ *
+ * Search: dbeel_gpu_reader_get's, bit for bit — the memtable first, reported
+ * at run == n_runs, then the tables newest index first, the first key match
+ * winning whatever the timestamps, filters consulted as there. hits[q] has
+ * exactly the fields reader_get gives (value_offset / value_len still
+ * describe the data bytes inside runs[run].data), and the five counters in
+ * stats are those reader_get reports for the same batch.
+ *
+ * Records: the record of a found key, TOMBSTONES INCLUDED, is the
+ * 24 + value_len bytes data_len:u64 | data | timestamp:i128 as stored (the
+ * entry's bytes from value_offset - 8 to its end); a tombstone is a 24-byte
+ * record; an absent key has an empty range. record_offsets is the exclusive
+ * prefix sum of the record sizes over ALL n_keys; hits and record_offsets are
+ * always delivered complete, whatever the cap, so the caller can size the
+ * next buffer.
+ *
+ * Paging, stateless: n_done is the largest d with
+ * record_offsets[d] <= records_cap; the records of queries [0, n_done) are in
+ * records[0 .. records_len); trailing absent queries add no bytes and count
+ * as done. With n_done < n_keys the caller calls again with the remaining
+ * keys. No device state survives the call, so nothing can go stale under a
+ * put, flush or compaction in between; the price is that the next call
+ * searches its keys again, about 2 % of a call. If record 0
+ * alone exceeds records_cap (n_done == 0 < n_keys; query 0 is then a hit) the
+ * call returns DBEEL_ERR_ITEM_TOO_LARGE — the scan's rule; DBEEL_OK with
+ * n_done == 0 would make a caller spin — with hits, record_offsets and page
+ * (n_done = records_len = 0, needed = its size) still filled.
+ *
+ * No byte of records at or beyond records_len is written, and no element
+ * beyond hits[n_keys-1] or record_offsets[n_keys]. n_keys == 0 succeeds with
+ * record_offsets[0] = 0 (when the array is given) and a zeroed page.
+ * Zero-length and duplicate keys are legal.
+ *
+ * Validated on the host before any device call, in this order, each
+ * DBEEL_ERR_INVALID_ARG: a NULL reader, buf or page; with n_keys > 0 a NULL
+ * keys, key_offsets, hits or record_offsets; NULL records with
+ * records_cap > 0; n_keys >= 2^32; key_offsets not ascending. On any failure
+ * the reader is as it was.
+ *
+ * Memory: the engine allocates no host memory for results and registers
+ * nothing itself; the copies are hipMemcpyAsync on the reader's stream
+ * straight into the caller's buffers, true async DMA when those are
+ * registered with dbeel_gpu_pin_host. Device scratch is the reader's own
+ * per-batch scratch, shared with reader_get (nothing is retained between
+ * calls), the record buffer sized by records_len, not by the cap; none of it
+ * counts in table_bytes. One mid-call sync, as reader_get has, fetches the
+ * offsets so the host finds n_done by bisection; a final sync ends the call.
+ * stats->gather_ms is the offset scan plus the record gather, stats->d2h_ms
+ * covers all copies to the caller. */
+typedef struct {
+    dbeel_lookup_hit* hits;           /* n_keys                              */
+    uint64_t*         record_offsets; /* n_keys + 1, exclusive               */
+    uint8_t*          records;        /* records_cap bytes; NULL allowed iff
+                                         records_cap == 0                    */
+    uint64_t          records_cap;
+} dbeel_get_buffers;                  /* all caller-owned, never freed here  */
+
+typedef struct {
+    uint64_t n_done;        /* leading queries whose records were delivered  */
+    uint64_t records_len;   /* == record_offsets[n_done]                     */
+    uint64_t records_total; /* == record_offsets[n_keys]                     */
+    uint64_t needed;        /* size of record n_done, 0 when n_done==n_keys  */
+} dbeel_get_page;
+
+int dbeel_gpu_reader_get_entries(dbeel_gpu_reader* reader,
+        const uint8_t* keys, const uint64_t* key_offsets, uint64_t n_keys,
+        const dbeel_get_buffers* buf, dbeel_get_page* page,
+        dbeel_get_stats* stats /* may be NULL */);
+
 /* ---- Live reader: the shared sstable list ----
  * The reference's LSMTree keeps one list of open sstables that reads,
  * flushes and compactions share: a flush pushes the new table
@@ -272,6 +351,23 @@ int dbeel_gpu_reader_compact_begin(dbeel_gpu_reader* reader,
         dbeel_reader_compact_stats* stats /* may be NULL */);
 int  dbeel_gpu_reader_compact_commit(dbeel_gpu_reader* reader, size_t out_pos);
 void dbeel_gpu_reader_compact_abort(dbeel_gpu_reader* reader);
+
+/* compact_fetch: copies the PENDING table's .data and .index bytes — the
+ * bytes compact_begin(out = ...) returns — into the caller's buffers with
+ * hipMemcpyAsync on the reader's stream (true async DMA when they are
+ * registered with dbeel_gpu_pin_host). No kernel runs and no host memory is
+ * allocated: a caller that wants the output in pinned memory uses
+ * compact_begin(out = NULL) followed by this call. It can be called any
+ * number of times between begin and commit / abort and changes nothing.
+ * *data_len / *index_len receive the output's sizes (0 for an empty output),
+ * d2h_ms (may be NULL) the copies' time. A NULL argument other than d2h_ms,
+ * or nothing pending: DBEEL_ERR_INVALID_ARG (lengths zeroed). A cap too
+ * small: DBEEL_ERR_ITEM_TOO_LARGE with *data_len / *index_len set to what is
+ * needed, nothing written to the buffers, the pending table kept. */
+int  dbeel_gpu_reader_compact_fetch(dbeel_gpu_reader* reader,
+        uint8_t* data, uint64_t data_cap, uint8_t* index, uint64_t index_cap,
+        uint64_t* data_len, uint64_t* index_len,
+        double* d2h_ms /* may be NULL */);
 
 /* ---- Paged migration scan over the resident tables ----
  * dbeel_gpu_scan (below) for runs the reader already holds: the AsyncIter

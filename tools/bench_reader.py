@@ -12,6 +12,12 @@ and checks that all three paths return identical hit records.
 
     python tools/bench_reader.py                  # -> profiles/reader_cfg3.json
 
+--entries measures only dbeel_gpu_reader_get (the baseline) against
+dbeel_gpu_reader_get_entries into a pageable buffer, into a pinned buffer and
+as a call-again loop with a pinned 64 MiB page, interleaved:
+
+    python tools/bench_reader.py --entries  # -> profiles/reader_get_entries.json
+
 Kernel times of the old and the new search kernel come from a profiler
 run of their own (tracing slows the host, so never mixed with the walls):
 
@@ -37,6 +43,7 @@ from dbeel_amd import engine  # noqa: E402
 from dbeel_amd.genruns import make_config  # noqa: E402
 
 DEFAULT_OUT = os.path.join(REPO, "profiles", "reader_cfg3.json")
+ENTRIES_OUT = os.path.join(REPO, "profiles", "reader_get_entries.json")
 U8P = ctypes.POINTER(ctypes.c_uint8)
 U64P = ctypes.POINTER(ctypes.c_uint64)
 
@@ -137,6 +144,143 @@ def bench_reader(lib, runs, blooms, batch, device, warmup, reps):
     return out, hits
 
 
+class EntryBuffers:
+    """Caller-owned buffers of one dbeel_gpu_reader_get_entries call."""
+
+    def __init__(self, n, cap, pinned):
+        self.hits = np.empty(n, dtype=engine.HIT_DTYPE)
+        self.roff = np.empty(n + 1, dtype=np.uint64)
+        self.rec = np.empty(max(cap, 1), dtype=np.uint8)
+        self.rec[:] = 0  # touched: no first-use page faults in the samples
+        self.cap = cap
+        self.pinned = pinned
+        if pinned:
+            for a in (self.hits, self.roff, self.rec):
+                engine.pin_host(a)
+
+    def buf(self, first_key=0):
+        return engine.GetBuffers(
+            self.hits[first_key:].ctypes.data_as(
+                ctypes.POINTER(engine.LookupHit)),
+            self.roff[first_key:].ctypes.data_as(U64P),
+            self.rec.ctypes.data_as(U8P), self.cap)
+
+    def release(self):
+        if self.pinned:
+            for a in (self.hits, self.roff, self.rec):
+                engine.unpin_host(a)
+
+
+def get_entries(lib, rd, batch, bufs, first_key=0):
+    """One dbeel_gpu_reader_get_entries over keys [first_key, n);
+    -> (rc, wall_ms, stats dict, page dict)."""
+    b = bufs.buf(first_key)
+    page = engine.GetPage()
+    st = engine.GetStats()
+    key_bytes = int(batch.off[1])  # fixed-width keys: offsets stay from 0
+    blob_p = ctypes.cast(ctypes.addressof(batch.blob_p.contents)
+                         + first_key * key_bytes, U8P)
+    t0 = time.perf_counter()
+    rc = lib.dbeel_gpu_reader_get_entries(
+        rd._h, blob_p, batch.off_p, batch.n - first_key, ctypes.byref(b),
+        ctypes.byref(page), ctypes.byref(st))
+    wall = (time.perf_counter() - t0) * 1e3
+    return rc, wall, st.as_dict(), page.as_dict()
+
+
+def paged_loop(lib, rd, batch, bufs, check_against=None):
+    """The call-again loop over the whole batch with a bufs.cap-byte page;
+    -> summed wall / stats and the number of calls."""
+    tot = {"wall_ms": 0.0, "search_ms": 0.0, "gather_ms": 0.0, "d2h_ms": 0.0,
+           "h2d_ms": 0.0, "calls": 0, "bytes": 0}
+    done = 0
+    while done < batch.n:
+        rc, wall, st, page = get_entries(lib, rd, batch, bufs, done)
+        if rc != 0:
+            raise engine.DbeelGpuError(rc,
+                                       lib.dbeel_gpu_last_error().decode())
+        if check_against is not None:
+            lo = tot["bytes"]
+            assert np.array_equal(bufs.rec[:page["records_len"]],
+                                  check_against[lo:lo + page["records_len"]])
+        tot["wall_ms"] += wall
+        for k in ("search_ms", "gather_ms", "d2h_ms", "h2d_ms"):
+            tot[k] += st[k]
+        tot["calls"] += 1
+        tot["bytes"] += page["records_len"]
+        done += page["n_done"]
+    return tot
+
+
+def bench_get_entries(lib, runs, batch, device, warmup, reps, page_bytes):
+    """reader_get (the untouched baseline) against get_entries into a
+    pageable and into a pinned buffer of records_total bytes, and the
+    call-again loop with a pinned page_bytes page — interleaved round by
+    round."""
+    fields = ("wall_ms", "search_ms", "gather_ms", "d2h_ms", "h2d_ms")
+    paths = ("reader_get", "entries_pageable", "entries_pinned",
+             "entries_paged_loop")
+    samples = {p: {f: [] for f in fields} for p in paths}
+    with engine.Reader(runs, device=device) as rd:
+        probe = EntryBuffers(batch.n, 0, False)
+        rc, _, _, page = get_entries(lib, rd, batch, probe)
+        assert rc in (0, 3), rc
+        total = page["records_total"]
+        pageable = EntryBuffers(batch.n, total, False)
+        pinned = EntryBuffers(batch.n, total, True)
+        loop = EntryBuffers(batch.n, page_bytes, True)
+        try:
+            checks = {}
+            for rnd in range(warmup + reps):
+                wall, st, hits = reader_get(lib, rd, batch)
+                st["wall_ms"] = wall
+                got = {"reader_get": st}
+                for name, bufs in (("entries_pageable", pageable),
+                                   ("entries_pinned", pinned)):
+                    rc, wall, st_e, page = get_entries(lib, rd, batch, bufs)
+                    if rc != 0:
+                        raise engine.DbeelGpuError(
+                            rc, lib.dbeel_gpu_last_error().decode())
+                    assert page["n_done"] == batch.n
+                    st_e["wall_ms"] = wall
+                    got[name] = st_e
+                first = rnd == 0
+                got["entries_paged_loop"] = paged_loop(
+                    lib, rd, batch, loop, pinned.rec if first else None)
+                if first:
+                    checks["hits_equal_reader_get"] = bool(
+                        np.array_equal(pageable.hits, hits)
+                        and np.array_equal(pinned.hits, hits))
+                    checks["records_pageable_equal_pinned"] = bool(
+                        np.array_equal(pageable.rec, pinned.rec)
+                        and np.array_equal(pageable.roff, pinned.roff))
+                    checks["loop_bytes_equal_one_shot"] = bool(
+                        got["entries_paged_loop"]["bytes"] == total)
+                    checks["counters_equal_reader_get"] = all(
+                        got["reader_get"][k] == got["entries_pinned"][k]
+                        for k in ("bloom_probes", "bloom_skips", "searches",
+                                  "hits", "tombstones"))
+                    values_len = got["reader_get"]["values_len"]
+                    loop_calls = got["entries_paged_loop"]["calls"]
+                if rnd < warmup:
+                    continue
+                for p in paths:
+                    for f in fields:
+                        samples[p][f].append(got[p][f])
+        finally:
+            for b in (pinned, loop):
+                b.release()
+    return {
+        "records_total": total, "values_len": values_len,
+        "records_over_values": total / values_len if values_len else None,
+        "page_bytes": page_bytes, "paged_loop_calls": loop_calls,
+        "pinned_buffers": "hits, record_offsets and records",
+        "paths": {p: {f: summarize(samples[p][f]) for f in fields}
+                  for p in paths},
+        "checks": checks,
+    }
+
+
 def run_bloom(run, device):
     with engine.Job([run], device=device) as job:
         job.run(True)
@@ -185,6 +329,12 @@ def main():
                     help="one old lookup + reader gets with and without "
                          "filters, nothing written: the program to put "
                          "under the kernel tracer")
+    ap.add_argument("--entries", action="store_true",
+                    help="only reader_get against get_entries (pageable, "
+                         "pinned, paged loop) -> "
+                         "profiles/reader_get_entries.json")
+    ap.add_argument("--page-mb", type=int, default=64,
+                    help="page of the --entries call-again loop, MiB")
     ap.add_argument("--kernel-stats", metavar="CSV",
                     help="merge a kernel-stats CSV into --out and exit")
     args = ap.parse_args()
@@ -206,6 +356,24 @@ def main():
     print(f"workload built in {time.perf_counter() - t0:.1f}s", flush=True)
     input_bytes = sum(d.nbytes + i.nbytes for d, i in runs)
     views, keepalive = engine._views(runs)
+
+    if args.entries:
+        out = (ENTRIES_OUT if args.out == DEFAULT_OUT else args.out)
+        res = {
+            "workload": "cfg3", "scale": args.scale, "n_runs": len(runs),
+            "input_bytes": input_bytes, "batch_keys": args.keys,
+            "present_frac": 0.5, "warmup": args.warmup, "reps": args.reps,
+            "method": "interleaved round by round; wall at the C ABI call, "
+                      "the rest HIP events; paged loop = sums over its calls",
+            **bench_get_entries(lib, runs, batch, args.device, args.warmup,
+                                args.reps, args.page_mb << 20),
+        }
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        json.dump(res, open(out, "w"), indent=1)
+        print(json.dumps(res))
+        if not all(res["checks"].values()):
+            sys.exit("get_entries disagrees with reader_get or with itself")
+        return
 
     if args.profile_pass:
         old_lookup(lib, views, len(runs), batch, args.device)

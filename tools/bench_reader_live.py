@@ -25,6 +25,13 @@ and max are recorded. The paths are checked against each other: equal
 output bytes, and equal answers to one get batch.
 
     python tools/bench_reader_live.py      # -> profiles/reader_live_cfg3.json
+
+--fetch-into measures only the output fetch: compact_begin(out) against
+compact_begin(out = NULL) + dbeel_gpu_reader_compact_fetch into pinned caller
+buffers, same method:
+
+    python tools/bench_reader_live.py --fetch-into
+                                           # -> profiles/reader_fetch_into.json
 """
 import argparse
 import ctypes
@@ -43,6 +50,7 @@ from dbeel_amd import engine  # noqa: E402
 from dbeel_amd.genruns import make_config  # noqa: E402
 
 DEFAULT_OUT = os.path.join(REPO, "profiles", "reader_live_cfg3.json")
+FETCH_OUT = os.path.join(REPO, "profiles", "reader_fetch_into.json")
 U8P = ctypes.POINTER(ctypes.c_uint8)
 
 
@@ -128,6 +136,95 @@ def live_round(lib, views, n, device, fetch, bloom, positions, keys=None):
     return out
 
 
+def fetch_into_round(lib, views, n, device, positions, darr, iarr):
+    """open -> begin(out = NULL) + compact_fetch into the caller's (pinned)
+    arrays + commit, timed -> close."""
+    h, open_ms = open_reader(lib, views, n, device)
+    st = engine.ReaderCompactStats()
+    dl, il = ctypes.c_uint64(), ctypes.c_uint64()
+    ms = ctypes.c_double()
+    try:
+        t0 = now_ms()
+        check(lib, lib.dbeel_gpu_reader_compact_begin(
+            h, positions, n, 1, 0, None, None, None, ctypes.byref(st)))
+        t1 = now_ms()
+        check(lib, lib.dbeel_gpu_reader_compact_fetch(
+            h, darr.ctypes.data_as(U8P), darr.size,
+            iarr.ctypes.data_as(U8P), iarr.size, ctypes.byref(dl),
+            ctypes.byref(il), ctypes.byref(ms)))
+        t2 = now_ms()
+        check(lib, lib.dbeel_gpu_reader_compact_commit(h, 0))
+        t3 = now_ms()
+    finally:
+        lib.dbeel_gpu_reader_close(h)
+    return {"open_ms": open_ms, "begin_ms": t1 - t0, "fetch_ms": t2 - t1,
+            "commit_ms": t3 - t2, "total_ms": t3 - t0,
+            "fetch_d2h_ms": ms.value, "stats": st.as_dict(),
+            "lens": (int(dl.value), int(il.value))}
+
+
+def bench_fetch_into(lib, runs, views, n, device, positions, warmup, reps,
+                     out_path):
+    """compact_begin(out) against compact_begin(out = NULL) + compact_fetch
+    into pinned caller buffers, interleaved round by round, every round from
+    a freshly opened reader."""
+    # the output is no larger than the input
+    darr = np.zeros(sum(d.nbytes for d, _ in runs), dtype=np.uint8)
+    iarr = np.zeros(sum(i.nbytes for _, i in runs), dtype=np.uint8)
+    engine.pin_host(darr)
+    engine.pin_host(iarr)
+    rows = {"begin_out": [], "begin_then_fetch_pinned": []}
+    checks = {}
+    try:
+        for rnd in range(warmup + reps):
+            first = rnd == 0
+            a = live_round(lib, views, n, device, True, False, positions,
+                           [b"k"] if first else None)
+            b = fetch_into_round(lib, views, n, device, positions, darr, iarr)
+            if first:
+                dl, il = b["lens"]
+                checks["bytes_identical"] = bool(
+                    np.array_equal(a["bytes"][0], darr[:dl])
+                    and np.array_equal(a["bytes"][1], iarr[:il]))
+                print("checks:", json.dumps(checks), flush=True)
+            if rnd < warmup:
+                continue
+            rows["begin_out"].append(a)
+            rows["begin_then_fetch_pinned"].append(b)
+            print(f"round {rnd - warmup + 1}/{reps}: begin(out) "
+                  f"{a['total_ms']:.1f} ms, begin + fetch_into "
+                  f"{b['total_ms']:.1f} ms", flush=True)
+    finally:
+        engine.unpin_host(darr)
+        engine.unpin_host(iarr)
+    fa, fb = rows["begin_out"], rows["begin_then_fetch_pinned"]
+    res = {
+        "workload": "cfg3", "n_runs": n,
+        "output_bytes": sum(fb[-1]["lens"]),
+        "timed_at": "C ABI calls, host wall clock; *d2h_ms are HIP events",
+        "warmup_rounds": warmup, "reps": reps,
+        "begin_out": {
+            "begin_ms": summarize([r["begin_ms"] for r in fa]),
+            "commit_ms": summarize([r["commit_ms"] for r in fa]),
+            "total_ms": summarize([r["total_ms"] for r in fa]),
+            "d2h_ms": summarize([r["stats"]["d2h_ms"] for r in fa]),
+        },
+        "begin_then_fetch_pinned": {
+            "begin_ms": summarize([r["begin_ms"] for r in fb]),
+            "fetch_ms": summarize([r["fetch_ms"] for r in fb]),
+            "commit_ms": summarize([r["commit_ms"] for r in fb]),
+            "total_ms": summarize([r["total_ms"] for r in fb]),
+            "d2h_ms": summarize([r["fetch_d2h_ms"] for r in fb]),
+        },
+        "checks": checks,
+    }
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    json.dump(res, open(out_path, "w"), indent=1)
+    print(json.dumps(res))
+    if not all(checks.values()):
+        sys.exit("compact_fetch and compact_begin(out) disagree")
+
+
 def baseline_round(lib, views, n, device, keys=None):
     """compact from host bytes -> open a reader over the output -> close."""
     res = engine.CompactResult()
@@ -172,17 +269,28 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--probe-keys", type=int, default=100_000)
     ap.add_argument("--out", default=DEFAULT_OUT)
+    ap.add_argument("--fetch-into", action="store_true",
+                    help="only compact_begin(out) against begin(out = NULL) "
+                         "+ compact_fetch into pinned buffers -> "
+                         "profiles/reader_fetch_into.json")
     args = ap.parse_args()
 
     lib = engine._load_reader()
     t0 = time.perf_counter()
     runs = make_config("cfg3", scale=args.scale)
-    keys = probe_keys(runs, args.probe_keys)
+    keys = [] if args.fetch_into else probe_keys(runs, args.probe_keys)
     print(f"workload built in {time.perf_counter() - t0:.1f}s", flush=True)
     n = len(runs)
     views, keepalive = engine._views(runs)
     positions = (ctypes.c_uint32 * n)(*range(n))
     input_bytes = sum(d.nbytes + i.nbytes for d, i in runs)
+
+    if args.fetch_into:
+        out = FETCH_OUT if args.out == DEFAULT_OUT else args.out
+        bench_fetch_into(lib, runs, views, n, args.device, positions,
+                         args.warmup, args.reps, out)
+        del keepalive
+        return
 
     # ---- compaction: live vs baseline, interleaved round by round ----
     variants = {"live_fetch": (True, False), "live_nofetch": (False, False),

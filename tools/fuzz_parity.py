@@ -141,7 +141,8 @@ def reader_trial(rng, runs, device):
     with Reader(runs, blooms=blooms, device=device) as rd:
         got = rd.get(queries)
         _, _, _, st = rd.get_raw(queries)
-        scan_why = paged_scan_step(rng, rd, runs, stored)
+        scan_why = (get_entries_step(rng, rd, runs, queries)
+                    or paged_scan_step(rng, rd, runs, stored))
         if got == exp and not scan_why:
             live_why = live_reader_step(rng, rd, runs, blooms, queries,
                                         device)
@@ -161,6 +162,40 @@ def reader_trial(rng, runs, device):
         for e in parse_run(d, i)[::17]:
             if not lsm.bloom_contains(blooms[r], e.key):
                 return f"filter of run {r} misses stored key {e.key.hex()}"
+    return None
+
+
+def get_entries_step(rng, rd, runs, queries):
+    """get_entries of the open reader against tests/get_entries_model: one
+    call at a random cap (hits, offsets, page and delivered bytes), then the
+    paged loop at a random page size (data and timestamps)."""
+    sys.path.insert(0, os.path.join(
+        os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import get_entries_model as gem
+    from dbeel_amd.engine import HIT_DTYPE, DbeelGpuError
+
+    model = gem.Model(runs)
+    ehits, eoff, erec, _, _ = model.expect(queries)
+    cap = int(rng.integers(0, eoff[-1] + 2))
+    _, _, _, erc, epage = model.expect(queries, cap)
+    try:
+        hits, roff, view, page, _ = rd.get_entries_raw(queries,
+                                                       records_cap=cap)
+        rc = 0
+    except DbeelGpuError as e:
+        rc, hits, roff, page = e.code, e.hits, e.record_offsets, e.page
+        view = np.zeros(0, dtype=np.uint8)
+    if rc != erc or page != epage:
+        return f"get_entries cap {cap}: rc {rc} page {page}, want {erc} {epage}"
+    if not np.array_equal(hits, gem.hits_array(ehits, HIT_DTYPE)):
+        return f"get_entries cap {cap}: hits differ from the model"
+    if roff.tolist() != eoff:
+        return f"get_entries cap {cap}: record_offsets differ from the model"
+    if view.tobytes() != erec[:epage["records_len"]]:
+        return f"get_entries cap {cap}: record bytes differ from the model"
+    page_bytes = int(rng.integers(0, 4096))
+    if rd.get_entries(queries, page_bytes=page_bytes) != model.entries(queries):
+        return f"get_entries page_bytes {page_bytes}: entries differ"
     return None
 
 

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Device-memory stability check: churn job create/run/fetch/destroy,
 streamed ingests (each creates ~per-chunk HIP events), batched jobs,
-scans, sliced compactions and resident readers (open / get x N / paged
+scans, sliced compactions and resident readers (open / get x N / get_entries
+at three page sizes / compact begin + compact_fetch x 2 into caller buffers +
+abort / paged
 scans begin + next + end, one left for close to end / insert / compact
 begin + abort + commit / write batches with fetch on and off, a filter,
 both order paths and a refused call / memtable put x N + get + fetch +
@@ -62,6 +64,10 @@ def main():
     for d, i in ri_b:
         pin_host(d)
         pin_host(i)
+    # caller buffers of compact_fetch: the data one pinned
+    fetch_d = np.empty(sum(d.nbytes for d, _ in runs), dtype=np.uint8)
+    fetch_i = np.empty(sum(i.nbytes for _, i in runs), dtype=np.uint8)
+    pin_host(fetch_d)
 
     probe_rng = np.random.default_rng(5)
     probe_keys = [bytes(probe_rng.integers(0, 256, 16, dtype=np.uint8))
@@ -104,6 +110,23 @@ def main():
                         device=0) as rd:
                 for n in (10, 4000, 100, 20_000):
                     rd.get(probe_keys[:n])
+                # get_entries at three caps: one page, a few pages, many
+                # (the record scratch is sized by each page, shared with
+                # get, and regrows); the results live in caller memory
+                for n, cap in ((20_000, 64 << 20), (20_000, 1 << 20),
+                               (2000, 1 << 10)):
+                    rd.get_entries(probe_keys[:n], page_bytes=cap)
+                # compact_fetch: the pending table copied out twice into
+                # caller buffers, one pinned, and a refused short one
+                rd.compact_begin([1, 2], True, fetch=False)
+                try:
+                    rd.compact_fetch_into(fetch_d[:8], fetch_i)
+                    raise SystemExit("compact_fetch accepted a short buffer")
+                except DbeelGpuError:
+                    pass
+                for _ in range(2):
+                    rd.compact_fetch_into(fetch_d, fetch_i)
+                rd.compact_abort()
                 # paged scans: begin / next x N / end with growing and
                 # shrinking windows and page buffers (scratch regrowth), a
                 # pinned one, and one abandoned mid-way for close to end
@@ -201,6 +224,7 @@ def main():
         for d, i in ri_b:
             unpin_host(d)
             unpin_host(i)
+        unpin_host(fetch_d)
         os.environ.pop("DBEEL_STREAM_CHUNK_MB", None)
     print(f"LEAKCHECK OK: {args.iters} iterations across every API path, "
           f"drift {(base - free_mem()) / 1e6:.1f} MB")
