@@ -61,6 +61,10 @@
  *                  plus a merge sort of the prefix-tied writes only),
  *                  deduplicated (last arrival wins) and encoded through
  *                  the arrival index straight into a new resident table.
+ *   k_page_*     : a scan page as that batch (put_entries, scan_apply):
+ *                  every entry validated, the masked-out ones compacted
+ *                  away, the same order stage with keys read in place,
+ *                  survivors copied verbatim or rewritten as tombstones.
  *   host side   : resident jobs, batched independent jobs (one launch
  *                  set, per-job output slicing), streamed pinned ingest
  *                  with copy/compute overlap, sliced compaction for
@@ -72,6 +76,7 @@
  * Build: hipcc --offload-arch=gfx950 -O3 -shared -fPIC dbeel_gpu.hip
  *        -o libdbeel_gpu.so
  */
+#include <chrono>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -3679,12 +3684,31 @@ struct BatchPair {
     uint32_t rsv;
 };
 
-/* The staged key blob, for compares by arrival index. */
+/* Where the keys lie, for compares by arrival index: the staged key blob
+ * addressed through koff (index == NULL), or a page of run-format entries
+ * (keys = its data, index = its 16-B records; key a at keys + off + 8 with
+ * key_size - 8 bytes — every record passed k_page_stage). n bounds the
+ * arrival indices. */
 struct BatchKeys {
     const uint8_t* keys;
     const uint64_t* koff;
     uint32_t n;
+    const uint8_t* index;
 };
+
+/* The one accessor both input shapes share. */
+__device__ __forceinline__ const uint8_t* batch_key(const BatchKeys& K,
+                                                    uint32_t a,
+                                                    uint64_t& klen) {
+    if (K.index) {
+        const uint8_t* rec = K.index + (uint64_t)a * 16;
+        klen = ld_u32(rec + 8) - 8;
+        return K.keys + ld_u64(rec) + 8;
+    }
+    const uint64_t o = K.koff[a];
+    klen = K.koff[a + 1] - o;
+    return K.keys + o;
+}
 
 /* Order of two writes whose 8-byte prefixes are EQUAL: when both keys are
  * longer than 8 bytes, cmp_keys on the bytes past them; otherwise the
@@ -3692,10 +3716,10 @@ struct BatchKeys {
  * lengths decide. */
 __device__ __forceinline__ int batch_cmp_tied(const BatchKeys& K, uint32_t a,
                                               uint32_t b) {
-    const uint64_t oa = K.koff[a], la = K.koff[a + 1] - oa;
-    const uint64_t ob = K.koff[b], lb = K.koff[b + 1] - ob;
-    if (la > 8 && lb > 8)
-        return cmp_keys(K.keys + oa + 8, la - 8, K.keys + ob + 8, lb - 8);
+    uint64_t la, lb;
+    const uint8_t* ka = batch_key(K, a, la);
+    const uint8_t* kb = batch_key(K, b, lb);
+    if (la > 8 && lb > 8) return cmp_keys(ka + 8, la - 8, kb + 8, lb - 8);
     return la < lb ? -1 : (la > lb ? 1 : 0);
 }
 
@@ -3716,8 +3740,9 @@ __global__ void k_batch_prefix(BatchKeys K, uint64_t* pfx, uint32_t* arr) {
     uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < K.n;
          i += stride) {
-        const uint64_t o = K.koff[i];
-        pfx[i] = key_prefix(K.keys + o, K.koff[i + 1] - o);
+        uint64_t klen;
+        const uint8_t* key = batch_key(K, i, klen);
+        pfx[i] = key_prefix(key, klen);
         arr[i] = i;
     }
 }
@@ -3761,24 +3786,31 @@ __global__ void k_batch_unpairs(uint32_t n, const BatchPair* in,
     }
 }
 
-/* Sorted write i survives iff it is the last one or its key differs from
- * its successor's (equal keys are adjacent, in arrival order: the last
- * arrival wins). src = keep flag | arrival index. */
-__global__ void k_batch_flag(BatchKeys K, const uint64_t* pfx,
+/* Sorted write i of n survives iff it is the last one or its key differs
+ * from its successor's (equal keys are adjacent, in arrival order: the last
+ * arrival wins). src = keep flag | arrival index. full_size is what the
+ * encode will write: from voff for the arrays, the page record's own for a
+ * page, and 32 + klen for a page applied as tombstones. */
+__global__ void k_batch_flag(BatchKeys K, uint32_t n, const uint64_t* pfx,
                              const uint32_t* arr, const uint64_t* voff,
-                             RankRec* rrec) {
+                             int tomb, RankRec* rrec) {
     uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < K.n;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += stride) {
         const uint32_t a = arr[i];
-        const uint64_t klen = K.koff[a + 1] - K.koff[a];
-        const uint64_t vlen = voff[a + 1] - voff[a];
-        const bool keep = i + 1 == K.n || pfx[i] != pfx[i + 1] ||
+        uint64_t klen;
+        (void)batch_key(K, a, klen);
+        const bool keep = i + 1 == n || pfx[i] != pfx[i + 1] ||
                           batch_cmp_tied(K, a, arr[i + 1]) != 0;
         RankRec r;
         r.src = (keep ? RR_KEEP : 0) | a;
         r.key_size = (uint32_t)(8 + klen);
-        r.full_size = (uint32_t)(32 + klen + vlen);
+        if (!K.index)
+            r.full_size = (uint32_t)(32 + klen + (voff[a + 1] - voff[a]));
+        else if (tomb)
+            r.full_size = (uint32_t)(32 + klen);
+        else
+            r.full_size = ld_u32(K.index + (uint64_t)a * 16 + 12);
         rrec[i] = r;
     }
 }
@@ -3876,6 +3908,7 @@ struct BatchStage {
         StepTotals tot;
         uint32_t tie_pos, tie_flag; /* of the last write: their sum is the
                                        tied count */
+        uint32_t err;               /* a page's stage: DERR_* bits */
     }* h = nullptr;               /* pinned                                */
     /* carved out of d_slab */
     uint8_t *keys, *vals, *ts;
@@ -3883,10 +3916,16 @@ struct BatchStage {
     uint32_t *arr[2], *tie, *tpos, *zero;
     RankRec* rrec;
     StepTotals* tot;
+    uint8_t* extra;               /* the caller's own piece                */
+    size_t tmp_bytes = 0;         /* of d_tmp                              */
     int cur = 0;                  /* pfx[cur] / arr[cur] hold the order    */
     uint64_t* dst_off() const { return pfx[cur ^ 1]; } /* free after order */
     uint32_t* pos() const { return tie; }              /* free after order */
-    uint32_t n = 0;
+    BatchKeys K = {};             /* the key source; K.n bounds arrivals   */
+    const uint8_t* d_dts = nullptr; /* a page applied as tombstones: their
+                                       timestamp, 16 B on the device       */
+    uint32_t n = 0;               /* writes ordered: K.n, or the page
+                                     entries its mask selected             */
     uint64_t n_surv = 0, total_bytes = 0, prefix_tied = 0;
 };
 
@@ -3901,7 +3940,7 @@ static void batch_release(BatchStage& b) {
 
 /* merge-sorts m pairs of b.d_pairs[0..m) into b.d_pairs[m..2m). */
 static int batch_merge_sort(BatchStage& b, uint64_t m, hipStream_t s) {
-    const BatchLess less = {{b.keys, b.koff, b.n}};
+    const BatchLess less = {b.K};
     size_t bytes = 0;
     HIP_CHECK(rocprim::merge_sort(nullptr, bytes, b.d_pairs, b.d_pairs + m, m,
                                   less, s));
@@ -3911,19 +3950,16 @@ static int batch_merge_sort(BatchStage& b, uint64_t m, hipStream_t s) {
     return DBEEL_OK;
 }
 
-/* Steps 1-4 on stream s: upload, prefixes, order, survivor flags and
- * scans; returns with the stream idle and n_surv / total_bytes /
- * prefix_tied known to the host. ev (NULL or 3 events) receives the marks
- * start | uploaded | ordered. The input was validated: in.n in [1, 2^31). */
-static int batch_order(BatchStage& b, const BatchIn& in, hipStream_t s,
-                       hipEvent_t* ev) {
-    const uint32_t n = b.n = (uint32_t)in.n;
-    const uint64_t kbytes = in.koff[n], vbytes = in.voff[n];
-    /* measured (DESIGN.md §4b-5): the single merge sort is the faster of
-     * the two on three of the four benchmark shapes, so it is the default */
-    const char* mode = getenv("DBEEL_BATCH_ORDER");
-    const bool merge_all = !(mode && strcmp(mode, "radix") == 0);
+static int batch_sort_flag(BatchStage& b, int tomb, uint64_t bound,
+                           hipStream_t s, hipEvent_t* ev);
 
+/* The slab and the rocPRIM scratch for n writes: the arrays' staging
+ * (kbytes of keys, vbytes of values; a page has no arrays and stages
+ * nothing of them) plus `extra` bytes for the caller, at b.extra. */
+static int batch_alloc(BatchStage& b, uint32_t n, bool arrays,
+                       uint64_t kbytes, uint64_t vbytes, uint64_t extra,
+                       hipStream_t s) {
+    const uint64_t na = arrays ? n : 0; /* per-write array staging */
     /* the slab: 16-B aligned pieces */
     uint64_t at = 0;
     auto carve = [&](uint64_t bytes) {
@@ -3932,9 +3968,9 @@ static int batch_order(BatchStage& b, const BatchIn& in, hipStream_t s,
         return o;
     };
     const uint64_t o_keys = carve(kbytes), o_vals = carve(vbytes),
-                   o_ts = carve((uint64_t)n * 16),
-                   o_koff = carve((uint64_t)(n + 1) * 8),
-                   o_voff = carve((uint64_t)(n + 1) * 8),
+                   o_ts = carve(na * 16),
+                   o_koff = carve(arrays ? (na + 1) * 8 : 0),
+                   o_voff = carve(arrays ? (na + 1) * 8 : 0),
                    o_pfx0 = carve((uint64_t)n * 8),
                    o_pfx1 = carve((uint64_t)n * 8),
                    o_arr0 = carve((uint64_t)n * 4),
@@ -3942,7 +3978,8 @@ static int batch_order(BatchStage& b, const BatchIn& in, hipStream_t s,
                    o_tie = carve((uint64_t)n * 4),
                    o_tpos = carve((uint64_t)n * 4),
                    o_rrec = carve((uint64_t)n * sizeof(RankRec)),
-                   o_tot = carve(sizeof(StepTotals)), o_zero = carve(16);
+                   o_tot = carve(sizeof(StepTotals)), o_zero = carve(16),
+                   o_extra = carve(extra);
     HIP_CHECK(hipMalloc(&b.d_slab, at));
     HIP_CHECK(hipHostMalloc(&b.h, sizeof *b.h));
     uint8_t* S = b.d_slab;
@@ -3960,6 +3997,7 @@ static int batch_order(BatchStage& b, const BatchIn& in, hipStream_t s,
     b.rrec = (RankRec*)(S + o_rrec);
     b.tot = (StepTotals*)(S + o_tot);
     b.zero = (uint32_t*)(S + o_zero);
+    b.extra = S + o_extra;
 
     /* one scratch buffer for the primitives whose size n alone decides */
     size_t t_radix = 0, t_scan = 0, t_surv = 0;
@@ -3972,6 +4010,20 @@ static int batch_order(BatchStage& b, const BatchIn& in, hipStream_t s,
     size_t tmp_bytes = t_radix > t_scan ? t_radix : t_scan;
     if (t_surv > tmp_bytes) tmp_bytes = t_surv;
     HIP_CHECK(hipMalloc(&b.d_tmp, tmp_bytes ? tmp_bytes : 1));
+    b.tmp_bytes = tmp_bytes;
+    return DBEEL_OK;
+}
+
+/* Steps 1-4 on stream s: upload, prefixes, order, survivor flags and
+ * scans; returns with the stream idle and n_surv / total_bytes /
+ * prefix_tied known to the host. ev (NULL or 3 events) receives the marks
+ * start | uploaded | ordered. The input was validated: in.n in [1, 2^31). */
+static int batch_order(BatchStage& b, const BatchIn& in, hipStream_t s,
+                       hipEvent_t* ev) {
+    const uint32_t n = b.n = (uint32_t)in.n;
+    const uint64_t kbytes = in.koff[n], vbytes = in.voff[n];
+    int rc = batch_alloc(b, n, true, kbytes, vbytes, 0, s);
+    if (rc) return rc;
 
     /* 1. upload */
     if (ev) HIP_CHECK(hipEventRecord(ev[0], s));
@@ -3990,11 +4042,28 @@ static int batch_order(BatchStage& b, const BatchIn& in, hipStream_t s,
     HIP_CHECK(hipMemsetAsync(b.zero, 0, 16, s));
     if (ev) HIP_CHECK(hipEventRecord(ev[1], s));
 
-    /* 2. prefixes, 3. order */
-    const BatchKeys K = {b.keys, b.koff, n};
+    /* 2. prefixes */
+    b.K = {b.keys, b.koff, n, nullptr};
+    hipLaunchKernelGGL(k_batch_prefix, dim3(pick_grid(n, 256)), dim3(256), 0,
+                       s, b.K, b.pfx[0], b.arr[0]);
+    return batch_sort_flag(b, 0, 32ull * n + kbytes + vbytes, s, ev);
+}
+
+/* Steps 3-4 over the b.n writes whose prefixes and arrival indices lie in
+ * b.pfx[0] / b.arr[0], keys read through b.K. bound = the most bytes the
+ * survivors can come to. ev as batch_order's: ev[2] is recorded here. */
+static int batch_sort_flag(BatchStage& b, int tomb, uint64_t bound,
+                           hipStream_t s, hipEvent_t* ev) {
+    const uint32_t n = b.n;
+    const BatchKeys& K = b.K;
+    const size_t tmp_bytes = b.tmp_bytes;
+    /* measured (DESIGN.md §4b-5): the single merge sort is the faster of
+     * the two on three of the four benchmark shapes, so it is the default */
+    const char* mode = getenv("DBEEL_BATCH_ORDER");
+    const bool merge_all = !(mode && strcmp(mode, "radix") == 0);
     const dim3 grid(pick_grid(n, 256)), block(256);
-    hipLaunchKernelGGL(k_batch_prefix, grid, block, 0, s, K, b.pfx[0],
-                       b.arr[0]);
+
+    /* 3. order */
     if (merge_all) {
         HIP_CHECK(hipMalloc(&b.d_pairs, 2ull * n * sizeof(BatchPair)));
         hipLaunchKernelGGL(k_batch_pairs, grid, block, 0, s, n, b.pfx[0],
@@ -4047,8 +4116,8 @@ static int batch_order(BatchStage& b, const BatchIn& in, hipStream_t s,
     if (ev) HIP_CHECK(hipEventRecord(ev[2], s));
 
     /* 4. survivors: flags, positions, byte offsets, totals */
-    hipLaunchKernelGGL(k_batch_flag, grid, block, 0, s, K, pfx, arr, b.voff,
-                       b.rrec);
+    hipLaunchKernelGGL(k_batch_flag, grid, block, 0, s, K, n, pfx, arr,
+                       (const uint64_t*)b.voff, tomb, b.rrec);
     {
         size_t tb = tmp_bytes;
         HIP_CHECK(survivor_scans(b.d_tmp, tb, b.rrec, b.dst_off(), b.pos(), n,
@@ -4064,7 +4133,7 @@ static int batch_order(BatchStage& b, const BatchIn& in, hipStream_t s,
     b.total_bytes = b.h->tot.total_out;
     /* what the encode kernel's stores are bounded by */
     if (b.n_surv == 0 || b.n_surv > n ||
-        b.total_bytes > 32ull * n + kbytes + vbytes ||
+        b.total_bytes > bound ||
         b.total_bytes < 32 * b.n_surv) {
         set_err("write batch: survivor totals %llu entries / %llu bytes are "
                 "impossible for %u writes", (unsigned long long)b.n_surv,
@@ -4074,9 +4143,108 @@ static int batch_order(BatchStage& b, const BatchIn& in, hipStream_t s,
     return DBEEL_OK;
 }
 
+/* ---- A page of run-format entries as the batch (put_entries) ---- */
+
+#define DERR_RANGE 4u /* a range id the take mask has no slot for */
+
+/* R = the page as one run. Per entry: the loader's bounds check and the
+ * consistency check (nothing is read through an entry that fails either),
+ * the key prefix, and the selection flag for the compaction that follows.
+ * The host reads err before any later kernel runs, so no kernel follows a
+ * rejected entry. */
+__global__ void k_page_stage(RunsDesc R, const uint32_t* rids,
+                             const uint8_t* take, uint32_t n_take,
+                             uint64_t* pfx, uint32_t* sel, uint32_t* err) {
+    const uint32_t n = (uint32_t)R.count[0];
+    uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += stride) {
+        EView e;
+        uint64_t p = 0;
+        uint32_t keep = 0;
+        if (!load_entry(R, 0, i, e) || !entry_consistent(R, 0, i, e)) {
+            atomicOr(err, DERR_CORRUPT);
+        } else {
+            p = key_prefix(e.key, e.klen);
+            if (!rids) {
+                keep = 1;
+            } else {
+                const uint32_t id = rids[i];
+                if (id >= n_take)
+                    atomicOr(err, DERR_RANGE);
+                else
+                    keep = take[id] ? 1u : 0u;
+            }
+        }
+        pfx[i] = p;
+        sel[i] = keep;
+    }
+}
+
+/* The selected entries, dense and still in arrival order: (prefix, arrival
+ * index) of entry i goes to slot spos[i]. Unselected entries end here. */
+__global__ void k_page_compact(uint32_t n, const uint64_t* pfx,
+                               const uint32_t* sel, const uint32_t* spos,
+                               uint64_t* pfx_out, uint32_t* arr_out) {
+    uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += stride) {
+        if (!sel[i]) continue;
+        const uint32_t o = spos[i];
+        pfx_out[o] = pfx[i];
+        arr_out[o] = i;
+    }
+}
+
+/* Wave per survivor. PUT (dts == NULL): the entry's bytes verbatim, one
+ * copy of full_size bytes — nothing is taken apart. DELETE: klen | key |
+ * 0 | dts, 32 + klen bytes (the size k_batch_flag scanned). Both write the
+ * survivor's index record. */
+__global__ void k_page_encode(uint32_t n, const RankRec* rrec,
+                              const uint64_t* dst_off, const uint32_t* pos,
+                              const uint8_t* data, const uint8_t* index,
+                              const uint8_t* dts, uint8_t* out_data,
+                              uint8_t* out_index) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
+    for (uint32_t i = wave; i < n; i += n_waves) {
+        const RankRec r = rrec[i];
+        if (!(r.src & RR_KEEP)) continue;
+        const uint32_t a = (uint32_t)r.src;
+        const uint8_t* src = data + ld_u64(index + (uint64_t)a * 16);
+        const uint64_t off = dst_off[i];
+        uint8_t* dst = out_data + off;
+        if (!dts) {
+            wave_copy_bytes(dst, src, r.full_size, lane);
+        } else {
+            const uint64_t klen = r.key_size - 8, zero = 0;
+            wave_copy_bytes(dst + 8, src + 8, klen, lane);
+            if (lane == 0) {
+                __builtin_memcpy(dst, &klen, 8);
+                __builtin_memcpy(dst + 8 + klen, &zero, 8);
+                __builtin_memcpy(dst + 16 + klen, dts, 16);
+            }
+        }
+        if (lane == 0) {
+            uint8_t* rec = out_index + (uint64_t)pos[i] * 16;
+            __builtin_memcpy(rec, &off, 8);
+            __builtin_memcpy(rec + 8, &r.key_size, 4);
+            __builtin_memcpy(rec + 12, &r.full_size, 4);
+        }
+    }
+}
+
 /* 5. encode into out_data (total_bytes) / out_index (n_surv records). */
 static void batch_encode(const BatchStage& b, hipStream_t s,
                          uint8_t* out_data, uint8_t* out_index) {
+    if (b.K.index) {
+        hipLaunchKernelGGL(k_page_encode,
+                           dim3(pick_grid((uint64_t)b.n * 64, 256)), dim3(256),
+                           0, s, b.n, b.rrec, b.dst_off(), b.pos(), b.K.keys,
+                           b.K.index, b.d_dts, out_data, out_index);
+        return;
+    }
     hipLaunchKernelGGL(k_batch_encode,
                        dim3(pick_grid((uint64_t)b.n * 64, 256)), dim3(256), 0,
                        s, b.n, b.rrec, b.dst_off(), b.pos(), b.keys, b.koff,
@@ -4402,39 +4570,20 @@ static inline uint64_t mem_run_bytes(uint64_t data_len, uint64_t count) {
     return data_len + count * 16 + 32;
 }
 
-extern "C" int dbeel_gpu_reader_put(dbeel_gpu_reader* rd, uint64_t n_writes,
-                                    const uint8_t* keys,
-                                    const uint64_t* key_offsets,
-                                    const uint8_t* values,
-                                    const uint64_t* value_offsets,
-                                    const uint8_t* timestamps,
-                                    dbeel_memtable_put_stats* stats) {
-    g_err[0] = 0;
-    if (stats) memset(stats, 0, sizeof *stats);
-    if (!rd) {
-        set_err("reader_put: null reader");
-        return DBEEL_ERR_INVALID_ARG;
-    }
-    const BatchIn in = {n_writes, keys, key_offsets, values, value_offsets,
-                        timestamps};
-    int rc = batch_check_arrays("reader_put", in);
-    if (rc) return rc;
-    uint64_t too_large = 0;
-    rc = batch_check_offsets("reader_put", in, &too_large);
-    if (rc) return rc;
-    ReaderMemtable& M = rd->mem;
-    if (M.count + in.n >= (1ull << 31)) {
-        set_err("reader_put: %llu memtable entries + %llu writes, at most "
-                "2^31 - 1 together (flush first)",
-                (unsigned long long)M.count, (unsigned long long)in.n);
-        return DBEEL_ERR_INVALID_ARG;
-    }
-    if (too_large != in.n) return batch_too_large("reader_put", too_large);
-    if (in.n == 0) return DBEEL_OK;
+/* What follows the order stage in every put: B (the ordered batch of b,
+ * encoded by batch_encode for its input shape) merged into the memtable,
+ * B winning equal keys, into the spare buffer; then the swap. rd->ev[0..2]
+ * were recorded by the caller's stages on rd->stream; on failure nothing
+ * of the memtable has changed. */
+struct MemMerged {
+    uint64_t batch_entries, replaced, entries, data_bytes;
+    float ms[3]; /* ev[0]-[1] | ev[1]-[3] | ev[3]-[4] */
+};
 
-    HIP_CHECK(hipSetDevice(rd->device));
+static int mem_merge(const char* who, dbeel_gpu_reader* rd, BatchStage& b,
+                     MemMerged& out) {
+    ReaderMemtable& M = rd->mem;
     hipStream_t s = rd->stream;
-    BatchStage b;
     uint8_t* d_brun = nullptr;   /* B: 16 B pad | data | index | 16 B pad */
     uint64_t* d_bpfx = nullptr;
     uint8_t* d_merge = nullptr;  /* the merge's scratch, carved below      */
@@ -4448,7 +4597,6 @@ extern "C" int dbeel_gpu_reader_put(dbeel_gpu_reader* rd, uint64_t n_writes,
     const bool displace = M.buf[M.cur ^ 1].hold != nullptr;
     ScopeGuard release([&] {
         (void)hipStreamSynchronize(s);
-        batch_release(b);
         (void)hipFree(d_brun);
         (void)hipFree(d_bpfx);
         (void)hipFree(d_merge);
@@ -4456,8 +4604,6 @@ extern "C" int dbeel_gpu_reader_put(dbeel_gpu_reader* rd, uint64_t n_writes,
         (void)hipFree(fresh.d_run);
         (void)hipFree(fresh.d_pfx);
     });
-    rc = batch_order(b, in, s, rd->ev);
-    if (rc) return rc;
 
     const uint64_t m = M.count, nb = b.n_surv;
     ReaderMemtable::Buf& spare = displace ? fresh : M.buf[M.cur ^ 1];
@@ -4554,9 +4700,9 @@ extern "C" int dbeel_gpu_reader_put(dbeel_gpu_reader* rd, uint64_t n_writes,
         /* what the copy's stores are bounded by */
         if (b.h->tot.err || new_count > N || new_count < (m > nb ? m : nb) ||
             new_len > in_bytes || new_len < 32 * new_count) {
-            set_err("reader_put: merge totals %llu entries / %llu bytes are "
+            set_err("%s: merge totals %llu entries / %llu bytes are "
                     "impossible for %llu + %llu entries (err %llu)",
-                    (unsigned long long)new_count,
+                    who, (unsigned long long)new_count,
                     (unsigned long long)new_len, (unsigned long long)m,
                     (unsigned long long)nb,
                     (unsigned long long)b.h->tot.err);
@@ -4591,18 +4737,285 @@ extern "C" int dbeel_gpu_reader_put(dbeel_gpu_reader* rd, uint64_t n_writes,
     M.count = new_count;
     M.data_len = new_len;
     M.puts++;
+    out.batch_entries = nb;
+    out.replaced = m + nb - new_count;
+    out.entries = new_count;
+    out.data_bytes = new_len;
+    for (int i = 0; i < 3; i++) out.ms[i] = ms[i];
+    return DBEEL_OK;
+}
+
+extern "C" int dbeel_gpu_reader_put(dbeel_gpu_reader* rd, uint64_t n_writes,
+                                    const uint8_t* keys,
+                                    const uint64_t* key_offsets,
+                                    const uint8_t* values,
+                                    const uint64_t* value_offsets,
+                                    const uint8_t* timestamps,
+                                    dbeel_memtable_put_stats* stats) {
+    g_err[0] = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (!rd) {
+        set_err("reader_put: null reader");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    const BatchIn in = {n_writes, keys, key_offsets, values, value_offsets,
+                        timestamps};
+    int rc = batch_check_arrays("reader_put", in);
+    if (rc) return rc;
+    uint64_t too_large = 0;
+    rc = batch_check_offsets("reader_put", in, &too_large);
+    if (rc) return rc;
+    ReaderMemtable& M = rd->mem;
+    if (M.count + in.n >= (1ull << 31)) {
+        set_err("reader_put: %llu memtable entries + %llu writes, at most "
+                "2^31 - 1 together (flush first)",
+                (unsigned long long)M.count, (unsigned long long)in.n);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (too_large != in.n) return batch_too_large("reader_put", too_large);
+    if (in.n == 0) return DBEEL_OK;
+
+    HIP_CHECK(hipSetDevice(rd->device));
+    hipStream_t s = rd->stream;
+    BatchStage b;
+    ScopeGuard release([&] {
+        (void)hipStreamSynchronize(s);
+        batch_release(b);
+    });
+    rc = batch_order(b, in, s, rd->ev);
+    if (rc) return rc;
+    MemMerged mm;
+    rc = mem_merge("reader_put", rd, b, mm);
+    if (rc) return rc;
     if (stats) {
-        stats->h2d_ms = ms[0];
-        stats->order_ms = ms[1];
-        stats->merge_ms = ms[2];
+        stats->h2d_ms = mm.ms[0];
+        stats->order_ms = mm.ms[1];
+        stats->merge_ms = mm.ms[2];
         stats->writes_in = b.n;
-        stats->batch_entries = nb;
-        stats->replaced = m + nb - new_count;
-        stats->entries = new_count;
-        stats->data_bytes = new_len;
+        stats->batch_entries = mm.batch_entries;
+        stats->replaced = mm.replaced;
+        stats->entries = mm.entries;
+        stats->data_bytes = mm.data_bytes;
         stats->prefix_tied = b.prefix_tied;
     }
     return DBEEL_OK;
+}
+
+/* ------------------------------------------------------------------ */
+/* Scan pages applied as puts or deletes (include/dbeel_gpu.h)         */
+/*                                                                    */
+/* The page replaces the five arrays as the batch's input:            */
+/*   k_page_stage   : validates every entry, prefix + selection flag. */
+/*   scan + k_page_compact : the selected entries, dense, in arrival  */
+/*                    order — the unselected end before the sort.     */
+/*   batch_sort_flag: the write batch's own order and survivor stages,*/
+/*                    keys read in place through batch_key.           */
+/*   k_page_encode  : wave per survivor, verbatim entry (PUT) or a    */
+/*                    tombstone built from its key (DELETE).          */
+/*   mem_merge      : what every put ends with.                       */
+/* ------------------------------------------------------------------ */
+
+struct PageIn {
+    const uint8_t* data;
+    uint64_t data_len;
+    const uint8_t* index;
+    uint64_t n;
+    const uint32_t* rids; /* NULL = every entry selected */
+    bool on_device;       /* the three lie on rd's device already */
+};
+
+/* The arguments passed the host checks: n in [1, 2^31), take / delete_ts
+ * are host memory. */
+static int put_entries_impl(const char* who, dbeel_gpu_reader* rd,
+                            const PageIn& pg, const uint8_t* take,
+                            uint32_t n_take, int mode,
+                            const uint8_t* delete_ts,
+                            dbeel_put_entries_stats* stats) {
+    HIP_CHECK(hipSetDevice(rd->device));
+    hipStream_t s = rd->stream;
+    const uint32_t n = (uint32_t)pg.n;
+    const int tomb = mode == DBEEL_APPLY_DELETE;
+    BatchStage b;
+    ScopeGuard release([&] {
+        (void)hipStreamSynchronize(s);
+        batch_release(b);
+    });
+    auto al16 = [](uint64_t v) { return (v + 15) & ~15ull; };
+    const uint64_t o_take = 0, o_dts = o_take + al16(pg.rids ? n_take : 0),
+                   o_err = o_dts + 16, o_data = o_err + 16,
+                   o_index = o_data + (pg.on_device ? 0 : al16(pg.data_len)),
+                   o_rids = o_index + (pg.on_device ? 0 : (uint64_t)n * 16),
+                   extra = o_rids + ((pg.on_device || !pg.rids)
+                                         ? 0 : al16((uint64_t)n * 4));
+    int rc = batch_alloc(b, n, false, 0, 0, extra, s);
+    if (rc) return rc;
+    uint8_t* d_take = b.extra + o_take;
+    uint8_t* d_dts = b.extra + o_dts;
+    uint32_t* d_err = (uint32_t*)(b.extra + o_err);
+    const uint8_t* d_data = pg.data;
+    const uint8_t* d_index = pg.index;
+    const uint32_t* d_rids = pg.rids;
+
+    /* 1. upload: the mask and the timestamp; a host page into the slab */
+    HIP_CHECK(hipEventRecord(rd->ev[0], s));
+    if (!pg.on_device) {
+        if (pg.data_len)
+            HIP_CHECK(hipMemcpyAsync(b.extra + o_data, pg.data, pg.data_len,
+                                     hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(b.extra + o_index, pg.index,
+                                 (uint64_t)n * 16, hipMemcpyHostToDevice, s));
+        d_data = b.extra + o_data;
+        d_index = b.extra + o_index;
+        if (pg.rids) {
+            HIP_CHECK(hipMemcpyAsync(b.extra + o_rids, pg.rids,
+                                     (uint64_t)n * 4, hipMemcpyHostToDevice,
+                                     s));
+            d_rids = (const uint32_t*)(b.extra + o_rids);
+        }
+    }
+    HIP_CHECK(hipEventRecord(rd->ev[1], s));
+    if (pg.rids)
+        HIP_CHECK(hipMemcpyAsync(d_take, take, n_take, hipMemcpyHostToDevice,
+                                 s));
+    if (tomb)
+        HIP_CHECK(hipMemcpyAsync(d_dts, delete_ts, 16, hipMemcpyHostToDevice,
+                                 s));
+    HIP_CHECK(hipMemsetAsync(d_err, 0, 16, s));
+    HIP_CHECK(hipMemsetAsync(b.zero, 0, 16, s));
+
+    /* 2. validate, prefixes, selection; the unselected are compacted away */
+    RunsDesc D;
+    memset(&D, 0, sizeof D);
+    D.n_runs = 1;
+    D.total = n;
+    D.data[0] = d_data;
+    D.index[0] = d_index;
+    D.data_len[0] = pg.data_len;
+    D.count[0] = n;
+    D.job_hi[0] = 1;
+    const dim3 grid(pick_grid(n, 256)), block(256);
+    hipLaunchKernelGGL(k_page_stage, grid, block, 0, s, D, d_rids,
+                       (const uint8_t*)d_take, n_take, b.pfx[1], b.tie,
+                       d_err);
+    {
+        size_t tb = b.tmp_bytes;
+        HIP_CHECK(rocprim::exclusive_scan(b.d_tmp, tb, b.tie, b.tpos,
+                                          (uint32_t)0, n,
+                                          rocprim::plus<uint32_t>(), s));
+    }
+    HIP_CHECK(hipMemcpyAsync(&b.h->tie_pos, b.tpos + (n - 1), 4,
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(&b.h->tie_flag, b.tie + (n - 1), 4,
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(&b.h->err, d_err, 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipGetLastError());
+    if (b.h->err & DERR_CORRUPT) {
+        set_err("%s: corrupt page (an index record out of bounds, "
+                "overlapping its successor, or disagreeing with the entry's "
+                "length fields)", who);
+        return DBEEL_ERR_CORRUPT;
+    }
+    if (b.h->err) {
+        set_err("%s: a range id is not below n_take = %u", who, n_take);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    const uint64_t n_sel = (uint64_t)b.h->tie_pos + b.h->tie_flag;
+    if (n_sel > n) {
+        set_err("%s: selected count %llu exceeds the %u entries", who,
+                (unsigned long long)n_sel, n);
+        return DBEEL_ERR_HIP;
+    }
+    if (stats) {
+        stats->entries_in = n;
+        stats->selected = n_sel;
+        stats->entries = rd->mem.count;
+        stats->data_bytes = rd->mem.data_len;
+    }
+    if (n_sel == 0) return DBEEL_OK; /* nothing selected: no put happened */
+    hipLaunchKernelGGL(k_page_compact, grid, block, 0, s, n,
+                       (const uint64_t*)b.pfx[1], (const uint32_t*)b.tie,
+                       (const uint32_t*)b.tpos, b.pfx[0], b.arr[0]);
+
+    /* 3-4. order and survivors, 5. encode + merge + swap */
+    b.K = {d_data, nullptr, n, d_index};
+    b.n = (uint32_t)n_sel;
+    b.d_dts = tomb ? d_dts : nullptr;
+    rc = batch_sort_flag(b, tomb, pg.data_len, s, rd->ev);
+    if (rc) return rc;
+    MemMerged mm;
+    rc = mem_merge(who, rd, b, mm);
+    if (rc) return rc;
+    if (stats) {
+        stats->h2d_ms = pg.on_device ? 0.0 : mm.ms[0];
+        stats->order_ms = mm.ms[1];
+        stats->merge_ms = mm.ms[2];
+        stats->batch_entries = mm.batch_entries;
+        stats->replaced = mm.replaced;
+        stats->entries = mm.entries;
+        stats->data_bytes = mm.data_bytes;
+        stats->prefix_tied = b.prefix_tied;
+    }
+    return DBEEL_OK;
+}
+
+/* Host checks of put_entries, in the header's order. */
+static int put_entries_check(const char* who, int mode,
+                             const uint8_t* delete_ts) {
+    if (mode != DBEEL_APPLY_PUT && mode != DBEEL_APPLY_DELETE) {
+        set_err("%s: unknown mode %d", who, mode);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (mode == DBEEL_APPLY_DELETE && !delete_ts) {
+        set_err("%s: DELETE needs delete_ts", who);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    return DBEEL_OK;
+}
+
+static int put_entries_count_check(const char* who, uint64_t n_mem,
+                                   uint64_t n) {
+    if (n >= (1ull << 31)) {
+        set_err("%s: %llu entries, at most 2^31 - 1 per page", who,
+                (unsigned long long)n);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (n_mem + n >= (1ull << 31)) {
+        set_err("%s: %llu memtable entries + %llu page entries, at most "
+                "2^31 - 1 together (flush first)", who,
+                (unsigned long long)n_mem, (unsigned long long)n);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    return DBEEL_OK;
+}
+
+extern "C" int dbeel_gpu_reader_put_entries(
+    dbeel_gpu_reader* rd, const uint8_t* data, uint64_t data_len,
+    const uint8_t* index, uint64_t n_entries, const uint32_t* range_ids,
+    const uint8_t* take, uint32_t n_take, int mode, const uint8_t* delete_ts,
+    dbeel_put_entries_stats* stats) {
+    g_err[0] = 0;
+    if (stats) memset(stats, 0, sizeof *stats);
+    const char* who = "reader_put_entries";
+    if (!rd) {
+        set_err("%s: null reader", who);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (n_entries && (!data || !index)) {
+        set_err("%s: null data or index", who);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    int rc = put_entries_check(who, mode, delete_ts);
+    if (rc) return rc;
+    if (range_ids && (!take || n_take == 0)) {
+        set_err("%s: range_ids need a take mask with n_take > 0", who);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    rc = put_entries_count_check(who, rd->mem.count, n_entries);
+    if (rc) return rc;
+    if (n_entries == 0) return DBEEL_OK;
+    const PageIn pg = {data, data_len, index, n_entries, range_ids, false};
+    return put_entries_impl(who, rd, pg, take, n_take, mode, delete_ts, stats);
 }
 
 extern "C" int dbeel_gpu_reader_memtable_info(const dbeel_gpu_reader* rd,
@@ -5986,28 +6399,26 @@ extern "C" int dbeel_gpu_reader_scan_snapshot(
 
 static inline uint64_t scan_align16(uint64_t v) { return (v + 15) & ~15ull; }
 
-extern "C" int dbeel_gpu_reader_scan_next(dbeel_gpu_reader_scan* sc,
-                                          uint8_t* data, size_t data_cap,
-                                          uint8_t* index, size_t index_cap,
-                                          uint32_t* range_ids,
-                                          dbeel_scan_page* page) {
-    g_err[0] = 0;
-    if (page) memset(page, 0, sizeof *page);
-    if (!sc || !page) {
-        set_err("reader_scan_next: null scan or page");
-        return DBEEL_ERR_INVALID_ARG;
-    }
-    if (!data || !index || data_cap == 0 || index_cap < 16) {
-        set_err("reader_scan_next: data and index buffers must be non-null, "
-                "data_cap > 0 and index_cap >= 16");
-        return DBEEL_ERR_INVALID_ARG;
-    }
+/* One page as drawn on the device, before anything is committed: the
+ * entries lie in rd->d_page, their records and range ids in the scan
+ * scratch, until the reader's next page. */
+struct ScanDrawn {
+    uint64_t taken, bytes, next; /* entries | data bytes | candidates */
+    bool shadow, done;           /* done: nothing was left to draw    */
+    const uint8_t* d_oidx;
+    const uint32_t* d_rido;
+    float ms[3];                 /* flag | emit | copy */
+};
+
+/* Draws the next page for scan_next and scan_apply (fn names the entry
+ * point in messages): everything up to and including the ITEM_TOO_LARGE
+ * verdict, with rd->stream idle on return and the cursor untouched. The
+ * stale check is the caller's. */
+static int scan_draw(const char* fn, dbeel_gpu_reader_scan* sc,
+                     uint64_t data_cap, uint64_t index_cap,
+                     dbeel_scan_page* page, ScanDrawn& out) {
     dbeel_gpu_reader* rd = sc->rd;
-    if (!sc->snapshot && sc->generation != rd->generation) {
-        set_err("reader_scan_next: stale scan (the table list changed since "
-                "scan_begin; start a new scan)");
-        return DBEEL_ERR_INVALID_ARG;
-    }
+    memset(&out, 0, sizeof out);
     /* a page is cut from ONE descriptor: the tables' (at most 64 runs), or
      * — once they are exhausted — the memtable segment's, a list of one.
      * The page that exhausts the tables may therefore be short. */
@@ -6016,6 +6427,7 @@ extern "C" int dbeel_gpu_reader_scan_next(dbeel_gpu_reader_scan* sc,
     if (m > sc->max_candidates) m = sc->max_candidates;
     if (m == 0) {
         page->done = 1;
+        out.done = true;
         return DBEEL_OK;
     }
     RunsDesc mem_desc;
@@ -6132,45 +6544,211 @@ extern "C" int dbeel_gpu_reader_scan_next(dbeel_gpu_reader_scan* sc,
     const uint64_t bytes = rd->h_scantot->st.total_out;
     const uint64_t next = rd->h_scantot->next;
     if (taken > max_entries || bytes > cap || next > m) {
-        set_err("reader_scan_next: inconsistent page totals");
+        set_err("%s: inconsistent page totals", fn);
         return DBEEL_ERR_HIP;
     }
     if (taken == 0 && next < m) {
         /* the first survivor alone exceeds data_cap (index_cap holds at
          * least one record): ItemTooLarge, cursor untouched */
         page->needed = rd->h_scantot->next_full;
-        set_err("reader_scan_next: entry of %llu bytes does not fit the "
-                "%zu-byte page buffer",
-                (unsigned long long)page->needed, data_cap);
+        set_err("%s: entry of %llu bytes does not fit the %llu-byte page "
+                "buffer", fn, (unsigned long long)page->needed,
+                (unsigned long long)data_cap);
         return DBEEL_ERR_ITEM_TOO_LARGE;
     }
+    for (int i = 0; i < 3; i++)
+        HIP_CHECK(hipEventElapsedTime(&out.ms[i], rd->ev[i], rd->ev[i + 1]));
+    out.taken = taken;
+    out.bytes = bytes;
+    out.next = next;
+    out.shadow = shadow;
+    out.d_oidx = d_oidx;
+    out.d_rido = d_rido;
+    sync_on_fail.dismiss();
+    return DBEEL_OK;
+}
+
+/* The page is done with: the cursor moves and the page record is filled. */
+static void scan_commit(dbeel_gpu_reader_scan* sc, const ScanDrawn& dr,
+                        float d2h_ms, dbeel_scan_page* page) {
+    sc->cursor += dr.next;
+    if (dr.shadow) sc->shadowed += sc->rd->h_scantot->shadowed;
+    page->data_len = dr.bytes;
+    page->n_entries = dr.taken;
+    page->candidates = dr.next;
+    page->done = sc->cursor == sc->total;
+    page->flag_ms = dr.ms[0];
+    page->emit_ms = dr.ms[1];
+    page->copy_ms = dr.ms[2];
+    page->d2h_ms = d2h_ms;
+}
+
+extern "C" int dbeel_gpu_reader_scan_next(dbeel_gpu_reader_scan* sc,
+                                          uint8_t* data, size_t data_cap,
+                                          uint8_t* index, size_t index_cap,
+                                          uint32_t* range_ids,
+                                          dbeel_scan_page* page) {
+    g_err[0] = 0;
+    if (page) memset(page, 0, sizeof *page);
+    if (!sc || !page) {
+        set_err("reader_scan_next: null scan or page");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (!data || !index || data_cap == 0 || index_cap < 16) {
+        set_err("reader_scan_next: data and index buffers must be non-null, "
+                "data_cap > 0 and index_cap >= 16");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    dbeel_gpu_reader* rd = sc->rd;
+    if (!sc->snapshot && sc->generation != rd->generation) {
+        set_err("reader_scan_next: stale scan (the table list changed since "
+                "scan_begin; start a new scan)");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    ScanDrawn dr;
+    int rc = scan_draw("reader_scan_next", sc, data_cap, index_cap, page, dr);
+    if (rc || dr.done) return rc;
+    hipStream_t s = rd->stream;
+    /* on failure nothing of this page may still be in flight into the
+     * caller's buffers */
+    ScopeGuard sync_on_fail([&] { (void)hipStreamSynchronize(s); });
     HIP_CHECK(hipEventRecord(rd->ev[4], s));
-    if (taken) {
-        HIP_CHECK(hipMemcpyAsync(data, rd->d_page, bytes,
+    if (dr.taken) {
+        HIP_CHECK(hipMemcpyAsync(data, rd->d_page, dr.bytes,
                                  hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipMemcpyAsync(index, d_oidx, taken * 16,
+        HIP_CHECK(hipMemcpyAsync(index, dr.d_oidx, dr.taken * 16,
                                  hipMemcpyDeviceToHost, s));
         if (sc->n_ranges && range_ids)
-            HIP_CHECK(hipMemcpyAsync(range_ids, d_rido, taken * 4,
+            HIP_CHECK(hipMemcpyAsync(range_ids, dr.d_rido, dr.taken * 4,
                                      hipMemcpyDeviceToHost, s));
     }
     HIP_CHECK(hipEventRecord(rd->ev[5], s));
     HIP_CHECK(hipStreamSynchronize(s));
     HIP_CHECK(hipGetLastError());
-    float ms[5] = {};
-    for (int i = 0; i < 5; i++)
-        HIP_CHECK(hipEventElapsedTime(&ms[i], rd->ev[i], rd->ev[i + 1]));
-    sc->cursor += next;
-    if (shadow) sc->shadowed += rd->h_scantot->shadowed;
-    page->data_len = bytes;
-    page->n_entries = taken;
-    page->candidates = next;
-    page->done = sc->cursor == sc->total;
-    page->flag_ms = ms[0];
-    page->emit_ms = ms[1];
-    page->copy_ms = ms[2];
-    page->d2h_ms = ms[4];
+    float d2h = 0;
+    HIP_CHECK(hipEventElapsedTime(&d2h, rd->ev[4], rd->ev[5]));
+    scan_commit(sc, dr, d2h, page);
     sync_on_fail.dismiss();
+    return DBEEL_OK;
+}
+
+extern "C" int dbeel_gpu_reader_scan_apply(
+    dbeel_gpu_reader_scan* sc, const dbeel_apply_action* actions,
+    size_t n_actions, const uint8_t* delete_ts, uint64_t page_bytes,
+    uint64_t page_entries, dbeel_scan_page* page,
+    dbeel_scan_apply_stats* stats) {
+    g_err[0] = 0;
+    if (page) memset(page, 0, sizeof *page);
+    if (stats) memset(stats, 0, sizeof *stats);
+    const char* who = "reader_scan_apply";
+    if (!sc || !page) {
+        set_err("%s: null scan or page", who);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (!actions) {
+        set_err("%s: null actions", who);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    dbeel_gpu_reader* rd = sc->rd;
+    const size_t want = sc->n_ranges ? sc->n_ranges : 1;
+    if (n_actions != want) {
+        set_err("%s: %zu actions for a scan of %u hash ranges (%zu needed)",
+                who, n_actions, sc->n_ranges, want);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    bool deletes = false;
+    for (size_t i = 0; i < n_actions; i++) {
+        const int k = actions[i].kind;
+        if (k != DBEEL_APPLY_SKIP && k != DBEEL_APPLY_PUT &&
+            k != DBEEL_APPLY_DELETE) {
+            set_err("%s: action %zu has unknown kind %d", who, i, k);
+            return DBEEL_ERR_INVALID_ARG;
+        }
+        deletes |= k == DBEEL_APPLY_DELETE;
+    }
+    for (size_t i = 0; i < n_actions; i++)
+        if (actions[i].kind != DBEEL_APPLY_SKIP && !actions[i].dst) {
+            set_err("%s: action %zu has no destination reader", who, i);
+            return DBEEL_ERR_INVALID_ARG;
+        }
+    for (size_t i = 0; i < n_actions; i++)
+        if (actions[i].kind != DBEEL_APPLY_SKIP &&
+            actions[i].dst->device != rd->device) {
+            set_err("%s: action %zu's destination is on device %d, the scan "
+                    "on device %d", who, i, actions[i].dst->device,
+                    rd->device);
+            return DBEEL_ERR_INVALID_ARG;
+        }
+    if (deletes && !delete_ts) {
+        set_err("%s: a DELETE action needs delete_ts", who);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (page_bytes == 0 || page_entries == 0) {
+        set_err("%s: page_bytes and page_entries must be > 0", who);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (!sc->snapshot && sc->generation != rd->generation) {
+        set_err("%s: stale scan (the table list changed since scan_begin; "
+                "start a new scan)", who);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    /* a page is one put: fewer than 2^31 entries */
+    if (page_entries > 0x7FFFFFFFull) page_entries = 0x7FFFFFFFull;
+
+    /* the groups: distinct (kind, dst) in order of their first range id */
+    struct Group {
+        int kind;
+        dbeel_gpu_reader* dst;
+        std::vector<uint8_t> take;
+    };
+    std::vector<Group> groups;
+    for (size_t i = 0; i < n_actions; i++) {
+        if (actions[i].kind == DBEEL_APPLY_SKIP) continue;
+        Group* g = nullptr;
+        for (Group& h : groups)
+            if (h.kind == actions[i].kind && h.dst == actions[i].dst) g = &h;
+        if (!g) {
+            groups.push_back(Group{actions[i].kind, actions[i].dst,
+                                   std::vector<uint8_t>(n_actions, 0)});
+            g = &groups.back();
+        }
+        g->take[i] = 1;
+    }
+
+    /* the page, finished on the scan reader's stream and left on the
+     * device; scan_draw returns with that stream idle */
+    ScanDrawn dr;
+    int rc = scan_draw(who, sc, page_bytes, page_entries * 16, page, dr);
+    if (rc || dr.done) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    uint64_t n_put = 0, n_del = 0, n_groups = 0;
+    if (dr.taken) {
+        const PageIn pg = {rd->d_page, dr.bytes, dr.d_oidx, dr.taken,
+                           sc->n_ranges ? dr.d_rido : nullptr, true};
+        for (Group& g : groups) {
+            rc = put_entries_count_check(who, g.dst->mem.count, dr.taken);
+            if (rc) return rc;
+            dbeel_put_entries_stats st;
+            memset(&st, 0, sizeof st);
+            /* returns with the destination's stream idle: the next page
+             * overwrites a buffer nobody reads */
+            rc = put_entries_impl(who, g.dst, pg, g.take.data(),
+                                  (uint32_t)n_actions, g.kind, delete_ts,
+                                  &st);
+            if (rc) return rc; /* earlier groups stay applied, cursor stays */
+            (g.kind == DBEEL_APPLY_PUT ? n_put : n_del) += st.selected;
+            n_groups++;
+        }
+    }
+    scan_commit(sc, dr, 0.0f, page);
+    if (stats) {
+        stats->apply_ms = std::chrono::duration<double, std::milli>(
+                              std::chrono::steady_clock::now() - t0).count();
+        stats->put_entries = n_put;
+        stats->delete_entries = n_del;
+        stats->skipped = dr.taken - n_put - n_del;
+        stats->groups = n_groups;
+    }
     return DBEEL_OK;
 }
 

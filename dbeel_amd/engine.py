@@ -515,6 +515,64 @@ class MemtableInfo(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class PutEntriesStats(ctypes.Structure):
+    """dbeel_put_entries_stats."""
+    _fields_ = [
+        ("h2d_ms", ctypes.c_double),
+        ("order_ms", ctypes.c_double),
+        ("merge_ms", ctypes.c_double),
+        ("entries_in", ctypes.c_uint64),
+        ("selected", ctypes.c_uint64),
+        ("batch_entries", ctypes.c_uint64),
+        ("replaced", ctypes.c_uint64),
+        ("entries", ctypes.c_uint64),
+        ("data_bytes", ctypes.c_uint64),
+        ("prefix_tied", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class ApplyAction(ctypes.Structure):
+    """dbeel_apply_action."""
+    _fields_ = [
+        ("kind", ctypes.c_int),
+        ("dst", ctypes.c_void_p),
+    ]
+
+
+class ScanApplyStats(ctypes.Structure):
+    """dbeel_scan_apply_stats."""
+    _fields_ = [
+        ("apply_ms", ctypes.c_double),
+        ("put_entries", ctypes.c_uint64),
+        ("delete_entries", ctypes.c_uint64),
+        ("skipped", ctypes.c_uint64),
+        ("groups", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+APPLY_SKIP = 0     # DBEEL_APPLY_SKIP
+APPLY_PUT = 1      # DBEEL_APPLY_PUT
+APPLY_DELETE = 2   # DBEEL_APPLY_DELETE
+_APPLY_KINDS = {"skip": APPLY_SKIP, "put": APPLY_PUT, "delete": APPLY_DELETE}
+
+
+def _ts16(ts):
+    """A timestamp (int, or 16 raw bytes) as a u8[16] array, i128 LE."""
+    if ts is None:
+        return None
+    raw = (bytes(ts) if isinstance(ts, (bytes, bytearray))
+           else int(ts).to_bytes(16, "little", signed=True))
+    if len(raw) != 16:
+        raise ValueError("a timestamp is 16 bytes")
+    return np.frombuffer(raw, dtype=np.uint8)
+
+
 _U8P = ctypes.POINTER(ctypes.c_uint8)
 _U64P = ctypes.POINTER(ctypes.c_uint64)
 _BATCH_ARGTYPES = [ctypes.c_uint64, _U8P, _U64P, _U8P, _U64P, _U8P]
@@ -640,6 +698,17 @@ def _load_reader() -> ctypes.CDLL:
             ctypes.c_void_p, _U8P, _U64P, ctypes.c_uint64,
             ctypes.POINTER(GetBuffers), ctypes.POINTER(GetPage),
             ctypes.POINTER(GetStats)]
+        lib.dbeel_gpu_reader_put_entries.restype = ctypes.c_int
+        lib.dbeel_gpu_reader_put_entries.argtypes = [
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+            ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p,
+            ctypes.POINTER(PutEntriesStats)]
+        lib.dbeel_gpu_reader_scan_apply.restype = ctypes.c_int
+        lib.dbeel_gpu_reader_scan_apply.argtypes = [
+            ctypes.c_void_p, ctypes.POINTER(ApplyAction), ctypes.c_size_t,
+            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
+            ctypes.POINTER(ScanPage), ctypes.POINTER(ScanApplyStats)]
         lib.dbeel_gpu_reader_compact_fetch.restype = ctypes.c_int
         lib.dbeel_gpu_reader_compact_fetch.argtypes = [
             ctypes.c_void_p, _U8P, ctypes.c_uint64, _U8P, ctypes.c_uint64,
@@ -749,6 +818,41 @@ class ReaderScan:
             err.page = pg.as_dict()
             raise err
         return pg.as_dict()
+
+    def apply(self, actions, page_bytes: int, page_entries=None,
+              delete_ts=None):
+        """Draws the next page as next() would into buffers of page_bytes
+        and page_entries records (default: one per 32 page bytes, the
+        smallest entry) and applies it on the device
+        (dbeel_gpu_reader_scan_apply): actions[id] is ("skip",),
+        ("put", reader) or ("delete", reader) for the entries whose first
+        matching hash range is id — one action for a scan without ranges.
+        delete_ts (int or 16 bytes) is the tombstones' timestamp. Returns
+        (page dict, stats dict); errors as next(), with the cursor where it
+        was."""
+        if not self._h:
+            raise ValueError("scan is closed")
+        acts = (ApplyAction * max(len(actions), 1))()
+        for i, a in enumerate(actions):
+            acts[i].kind = _APPLY_KINDS.get(a[0], a[0])
+            dst = a[1] if len(a) > 1 else None
+            if dst is not None and not dst._h:
+                raise ValueError("destination reader is closed")
+            acts[i].dst = None if dst is None else dst._h
+        if page_entries is None:
+            page_entries = max(1, int(page_bytes) // 32)
+        ts = _ts16(delete_ts)
+        pg = ScanPage()
+        st = ScanApplyStats()
+        rc = self._lib.dbeel_gpu_reader_scan_apply(
+            self._h, acts, len(actions),
+            None if ts is None else ts.ctypes.data, int(page_bytes),
+            int(page_entries), ctypes.byref(pg), ctypes.byref(st))
+        if rc != 0:
+            err = DbeelGpuError(rc, self._lib.dbeel_gpu_last_error().decode())
+            err.page = pg.as_dict()
+            raise err
+        return pg.as_dict(), st.as_dict()
 
     def info(self) -> dict:
         """dbeel_scan_snapshot_info as a dict: the snapshot's segments and
@@ -917,6 +1021,66 @@ class Reader:
         del keepalive
         self._check(rc)
         return st.as_dict()
+
+    def put_entries(self, data, index, range_ids=None, take=None,
+                    delete_ts=None):
+        """Puts a page exactly as a paged scan yields it — numpy arrays
+        data (u8), index (u8, 16 B per record) and optionally range_ids
+        (u32, one per record) with take (u8, take[id] != 0 selects), passed
+        through by pointer so pinned arrays work — into the memtable, in
+        page order, under put()'s contract. With delete_ts (int or 16 bytes)
+        every selected entry becomes a tombstone with that timestamp
+        instead (dbeel_gpu_reader_put_entries). Returns the stats dict; on
+        failure the memtable is unchanged."""
+        if not self._h:
+            raise ValueError("reader is closed")
+        n = index.nbytes // 16
+        if range_ids is not None and range_ids.nbytes // 4 < n:
+            raise ValueError("range_ids needs one slot per index record")
+        if take is not None:
+            take = np.ascontiguousarray(take, dtype=np.uint8)
+        ts = _ts16(delete_ts)
+        st = PutEntriesStats()
+        rc = self._lib.dbeel_gpu_reader_put_entries(
+            self._h, data.ctypes.data, data.nbytes, index.ctypes.data, n,
+            None if range_ids is None else range_ids.ctypes.data,
+            None if take is None else take.ctypes.data,
+            0 if take is None else take.size,
+            APPLY_PUT if ts is None else APPLY_DELETE,
+            None if ts is None else ts.ctypes.data, ctypes.byref(st))
+        self._check(rc)
+        return st.as_dict()
+
+    def migrate(self, actions, start_key=None, end_key=None,
+                hash_ranges=None, flags: int = SCAN_MEMTABLE,
+                page_bytes: int = 64 << 20, delete_ts=None,
+                max_candidates: int = 0):
+        """The migration loop inside HBM: opens a snapshot scan with
+        `flags` (SCAN_MEMTABLE | SCAN_NEWEST_ONLY), applies page after page
+        with ReaderScan.apply(actions, ...) until done, and returns the
+        summed stats: pages, entries, put_entries, delete_entries, skipped,
+        groups, apply_ms and the pages' flag / emit / copy ms."""
+        total = {"pages": 0, "entries": 0, "put_entries": 0,
+                 "delete_entries": 0, "skipped": 0, "groups": 0,
+                 "apply_ms": 0.0, "flag_ms": 0.0, "emit_ms": 0.0,
+                 "copy_ms": 0.0}
+        sc = ReaderScan(self, start_key, end_key, hash_ranges,
+                        max_candidates, snapshot_flags=int(flags))
+        try:
+            while True:
+                pg, st = sc.apply(actions, page_bytes, delete_ts=delete_ts)
+                total["pages"] += 1
+                total["entries"] += pg["n_entries"]
+                for k in ("put_entries", "delete_entries", "skipped",
+                          "groups", "apply_ms"):
+                    total[k] += st[k]
+                for k in ("flag_ms", "emit_ms", "copy_ms"):
+                    total[k] += pg[k]
+                if pg["done"]:
+                    break
+        finally:
+            sc.close()
+        return total
 
     @property
     def memtable_info(self) -> dict:

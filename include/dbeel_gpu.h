@@ -722,6 +722,120 @@ int  dbeel_gpu_reader_memtable_flush(dbeel_gpu_reader* reader, int build_bloom,
         uint8_t** bloom_bytes, uint64_t* bloom_len /* both or neither */);
 void dbeel_gpu_reader_memtable_clear(dbeel_gpu_reader* reader);
 
+/* ---- Scan pages applied as puts or deletes (migration inside HBM) ----
+ * The receiving end of the migration loop (tasks/migration.rs:62-131): per
+ * iterated entry the reference picks the first matching hash range, looks up
+ * that range's action and either sends Set(key, data, timestamp) to another
+ * shard — whose set_with_timestamp (shards.rs:768) replaces whatever the
+ * timestamps are — or calls tree.delete(key) on its own tree.
+ *
+ * put_entries: takes a page exactly as dbeel_gpu_reader_scan_next writes it:
+ * n_entries entries in the run entry format in data (data_len bytes), their
+ * 16-byte index records in index with offsets from 0, monotone and
+ * non-overlapping, in arrival order (= index order); keys unsorted and
+ * possibly repeated. Entry i is selected when range_ids == NULL or
+ * take[range_ids[i]] != 0. Under DBEEL_APPLY_PUT the memtable afterwards is
+ * the memtable after dbeel_gpu_reader_put of the selected entries, decoded
+ * and in page order (last arrival wins whatever the timestamps are,
+ * tombstones kept, bytes equal to dbeel_gpu_flush_batch of all arrivals
+ * since the last flush); a survivor is the verbatim bytes of its page entry.
+ * Under DBEEL_APPLY_DELETE it is the memtable after a put of (key, empty
+ * value, delete_ts) for every selected entry — tree.delete(key) per yielded
+ * entry. Documented divergence: the whole call carries ONE timestamp, where
+ * the reference reads the clock per delete. Gets, flush, fetch, snapshot
+ * scans and holds behave as after a put; DBEEL_BATCH_ORDER applies.
+ *
+ * Validated on the host before any device call, in this order: NULL reader;
+ * NULL data or index with n_entries != 0; a mode other than the two
+ * defined; DELETE without delete_ts; range_ids without take or with
+ * n_take == 0; n_entries >= 2^31; memtable entries + n_entries >= 2^31 (all
+ * DBEEL_ERR_INVALID_ARG). n_entries == 0 is a successful no-op.
+ *
+ * Validated on the device (one implementation serves host pages and pages
+ * already resident, see scan_apply): every entry, selected or not, passes
+ * the run loader's bounds check and consistency check (offset and sizes
+ * inside data_len, the bincode length fields agreeing with the index
+ * record, the successor's offset not overlapping) before anything is read
+ * through it; a failing entry is DBEEL_ERR_CORRUPT. A selected entry with
+ * range_ids[i] >= n_take is DBEEL_ERR_INVALID_ARG. On these and on every
+ * other failure the reader, its memtable and its answers are exactly as
+ * before. A call that selects nothing is a successful no-op:
+ * memtable_info.puts does not move.
+ *
+ * Stats: as dbeel_memtable_put_stats; entries_in = n_entries, selected =
+ * entries the mask let through, h2d_ms = 0 for a device-resident page.
+ *
+ * scan_apply: draws the next page exactly as dbeel_gpu_reader_scan_next
+ * would with data_cap = page_bytes and index_cap = 16 * page_entries
+ * (cursor rule, done, the ITEM_TOO_LARGE protocol with page->needed,
+ * stale-scan refusal, snapshot behaviour and the shadow pass are the same),
+ * leaves it in the reader's device page buffer and applies it there:
+ * actions[id] says what happens to the entries whose first matching range
+ * is id; n_actions must equal the scan's n_ranges, and a scan without hash
+ * ranges takes n_actions == 1 with every entry under actions[0]. SKIP drops
+ * the entry (a caller with a remote destination scans those ranges with
+ * scan_next); PUT goes to dst's memtable; DELETE puts a tombstone carrying
+ * delete_ts into dst's memtable — normally the scan's own reader, as in the
+ * reference. Entries are grouped by distinct (kind, dst), in ascending order
+ * of each group's first range id; each group is one device run of
+ * put_entries over the same resident page with that group's take mask.
+ * page->d2h_ms is 0. dst may be the scan's own reader: puts bump no
+ * generation and snapshot scans hold their buffers.
+ *
+ * Refused before any device call (DBEEL_ERR_INVALID_ARG, the cursor and
+ * everything else untouched), in this order: NULL scan or page (page and
+ * stats are zeroed first); NULL actions; n_actions mismatch; an unknown
+ * kind; PUT or DELETE with a NULL dst; a dst on another device than the
+ * scan's reader; DELETE without delete_ts; page_bytes == 0 or
+ * page_entries == 0; a stale scan.
+ *
+ * Failure: the cursor advances only after every group succeeded. If group g
+ * fails, the groups before it stay applied and the cursor stays; calling
+ * again re-applies the same page, which for a destination that took no
+ * other writes in between reaches the same state because a set replaces —
+ * the reference's re-send.
+ *
+ * Streams: the page is finished on the scan reader's stream, which is
+ * synchronised before any destination's stream reads it; each destination
+ * is synchronised before the call returns, so the next page overwrites a
+ * buffer nobody reads. */
+#define DBEEL_APPLY_SKIP   0
+#define DBEEL_APPLY_PUT    1
+#define DBEEL_APPLY_DELETE 2
+
+typedef struct {
+    double   h2d_ms, order_ms, merge_ms;  /* as dbeel_memtable_put_stats; order_ms
+                 covers stage + order + encode                                   */
+    uint64_t entries_in, selected;        /* page entries | those the mask took   */
+    uint64_t batch_entries, replaced;     /* as dbeel_memtable_put_stats          */
+    uint64_t entries, data_bytes;         /* memtable after the call              */
+    uint64_t prefix_tied;
+} dbeel_put_entries_stats;
+
+int  dbeel_gpu_reader_put_entries(dbeel_gpu_reader* reader,
+        const uint8_t* data, uint64_t data_len,
+        const uint8_t* index, uint64_t n_entries,     /* 16-B records */
+        const uint32_t* range_ids /* NULL = every entry selected */,
+        const uint8_t* take, uint32_t n_take,         /* take[id] != 0 selects */
+        int mode /* DBEEL_APPLY_PUT | DBEEL_APPLY_DELETE */,
+        const uint8_t* delete_ts /* 16 B, i128 LE; DELETE only */,
+        dbeel_put_entries_stats* stats /* may be NULL */);
+
+typedef struct { int kind; dbeel_gpu_reader* dst; } dbeel_apply_action;
+
+typedef struct {
+    double   apply_ms;                    /* wall: page drawn -> last group merged */
+    uint64_t put_entries, delete_entries; /* page entries under each kind         */
+    uint64_t skipped;                     /* page entries under SKIP              */
+    uint64_t groups;                      /* device runs of put_entries           */
+} dbeel_scan_apply_stats;
+
+int  dbeel_gpu_reader_scan_apply(dbeel_gpu_reader_scan* scan,
+        const dbeel_apply_action* actions, size_t n_actions,
+        const uint8_t* delete_ts /* needed iff some kind is DELETE */,
+        uint64_t page_bytes, uint64_t page_entries,
+        dbeel_scan_page* page, dbeel_scan_apply_stats* stats /* may be NULL */);
+
 /* ---- Resident-job API (benchmarking / repeated compactions) ----
  * Uploads the runs to `device` once; each run executes the device pipeline
  * with inputs already resident in HBM (what BASELINE's MB/s is quoted on)

@@ -142,7 +142,8 @@ def reader_trial(rng, runs, device):
         got = rd.get(queries)
         _, _, _, st = rd.get_raw(queries)
         scan_why = (get_entries_step(rng, rd, runs, queries)
-                    or paged_scan_step(rng, rd, runs, stored))
+                    or paged_scan_step(rng, rd, runs, stored)
+                    or migrate_step(rng, rd, runs, device))
         if got == exp and not scan_why:
             live_why = live_reader_step(rng, rd, runs, blooms, queries,
                                         device)
@@ -236,6 +237,61 @@ def paged_scan_step(rng, rd, runs, stored):
                 for e in parse_run(md, mi)]
         if ids.tolist() != want:
             return f"paged scan {kw} {paging}: range ids differ"
+    return None
+
+
+def migrate_step(rng, rd, runs, device):
+    """One random migrate of the open reader (its memtable is empty here):
+    random hash ranges with a random action each — skip, put into one of two
+    destination readers, delete into the second — small random pages, plain
+    or NEWEST_ONLY, either order path, against tests/migrate_model over the
+    snapshot model's yield."""
+    sys.path.insert(0, os.path.join(
+        os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import migrate_model
+    import snapshot_model
+    from dbeel_amd.engine import SCAN_MEMTABLE, SCAN_NEWEST_ONLY, Reader
+
+    if not any(len(i) for _, i in runs):
+        return None
+    n = int(rng.integers(1, 5))
+    ranges = [(int(rng.integers(0, 2**32)), int(rng.integers(0, 2**32)))
+              for _ in range(n)]
+    newest = bool(rng.integers(0, 2))
+    dts = int(rng.integers(-2**62, 2**62))
+    segs = snapshot_model.segments(runs)
+    model = snapshot_model.snapshot_model(segs, hash_ranges=ranges,
+                                          newest_only=newest)
+    page = migrate_model.decode_page(model[0], model[1])
+    rids = snapshot_model.first_range_ids(model, ranges)
+    kinds = [("skip",), ("put", "A"), ("put", "B"), ("delete", "B")]
+    named = [kinds[int(rng.integers(0, len(kinds)))] for _ in range(n)]
+    want = migrate_model.migrate([(page, rids)], named, dts)
+    order = ("radix", "merge")[int(rng.integers(0, 2))]
+    paging = dict(page_bytes=int(rng.integers(459, 20000)),
+                  max_candidates=int(rng.choice([0, 63, 64, 65, 1000])))
+    what = f"migrate {ranges} {named} newest={newest} {paging} order={order}"
+    nonempty = next(r for r in runs if len(r[1]))
+    os.environ["DBEEL_BATCH_ORDER"] = order
+    try:
+        with Reader([nonempty], device=device) as A, \
+                Reader([nonempty], device=device) as B:
+            dst = {"A": A, "B": B}
+            acts = [(a[0],) if a[0] == "skip" else (a[0], dst[a[1]])
+                    for a in named]
+            st = rd.migrate(acts, hash_ranges=ranges, delete_ts=dts,
+                            flags=SCAN_MEMTABLE
+                            | (SCAN_NEWEST_ONLY if newest else 0), **paging)
+            if st["entries"] != len(page):
+                return f"{what}: {st['entries']} entries, model {len(page)}"
+            for name, r in dst.items():
+                exp = want[name].run() if name in want else (b"", b"")
+                if r.memtable_fetch() != exp:
+                    return f"{what}: memtable of {name} differs from the model"
+    finally:
+        os.environ.pop("DBEEL_BATCH_ORDER", None)
+    if rd.held_bytes:
+        return f"{what}: {rd.held_bytes} bytes still held"
     return None
 
 

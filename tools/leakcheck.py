@@ -10,7 +10,9 @@ both order paths and a refused call / memtable put x N + get + fetch +
 flush + clear, with the storage pair checked never to shrink nor to regrow
 after a flush / snapshot scans begun, paged and ended across an insert, two
 puts and a compaction, one left for close / close with a non-empty
-memtable), reporting hipMemGetInfo drift. A leak in any path shows as monotonically shrinking free memory.
+memtable / put_entries of a host page, a refused corrupt page, scan_apply
+into a second reader with deletes back into the source, flushes, close with
+that scan open), reporting hipMemGetInfo drift. A leak in any path shows as monotonically shrinking free memory.
 
     python tools/leakcheck.py --iters 40
 """
@@ -208,6 +210,36 @@ def main():
                     raise SystemExit("the open snapshot holds nothing")
                 rd.compact_begin([0, 1], True, fetch=False)
                 # close aborts that, ends snaps[2] and frees the memtable
+            # migration inside HBM: a host page through put_entries, a
+            # refused corrupt page, scan pages applied into a second reader
+            # and as deletes back into the source (staging and merge scratch
+            # are each call's; the displaced memtable buffer is the scan's),
+            # both memtables flushed, and close with the scan still open
+            with Reader(runs[:2], device=0) as src, \
+                    Reader(runs2[:1], device=0) as dst:
+                pd, px, _ = src.scan(end_key=b"\x20", page_bytes=1 << 22)
+                pd = np.frombuffer(pd, dtype=np.uint8)
+                px = np.frombuffer(px, dtype=np.uint8).copy()
+                dst.put_entries(pd, px)
+                bad = px.copy()
+                bad[16 + 8:16 + 12] = 0  # key_size 0 in the second record
+                try:
+                    dst.put_entries(pd, bad)
+                    raise SystemExit("put_entries accepted a corrupt page")
+                except DbeelGpuError:
+                    pass
+                halves = [(0, 1 << 31), (1 << 31, 0xFFFFFFFF)]
+                src.put(batch[:3000])
+                mig = src.snapshot_open(hash_ranges=halves, memtable=True,
+                                        max_candidates=6000)
+                for _ in range(4):
+                    mig.apply([("put", dst), ("delete", src)], 1 << 20,
+                              delete_ts=it)
+                if not src.held_bytes:
+                    raise SystemExit("deletes displaced no held buffer")
+                dst.memtable_flush(fetch=False)
+                src.memtable_flush(fetch=False)
+                # close ends mig and frees what it holds
             flush_batch(batch[:7000], device=0)
             f = free_mem()
             if base is None:
