@@ -13,6 +13,7 @@ from .engine import (  # noqa: F401
     Job,
     Reader,
     compact,
+    compact_into,
     compact_sliced,
     encode_run,
     flush_batch,
@@ -24,7 +25,7 @@ from .engine import (  # noqa: F401
 )
 
 __all__ = [
-    "compact", "compact_sliced", "scan", "lookup", "encode_run",
+    "compact", "compact_sliced", "compact_into", "scan", "lookup", "encode_run",
     "Job", "BatchJob", "pin_host", "unpin_host", "DbeelGpuError", "format",
     "Reader", "lookup_raw", "flush_batch",
 ]

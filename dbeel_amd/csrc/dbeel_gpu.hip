@@ -65,6 +65,11 @@
  *                  every entry validated, the masked-out ones compacted
  *                  away, the same order stage with keys read in place,
  *                  survivors copied verbatim or rewritten as tombstones.
+ *   k_index_rebase / k_bloom_hash / k_bloom_fill : compaction into
+ *                  caller buffers in pipelined key slices — index offsets
+ *                  rebased on the device on the way in (-slice start) and
+ *                  out (+running output offset, in scratch), the "DBLM"
+ *                  filter built across slices from appended hashes.
  *   host side   : resident jobs, batched independent jobs (one launch
  *                  set, per-job output slicing), streamed pinned ingest
  *                  with copy/compute overlap, sliced compaction for
@@ -1549,6 +1554,22 @@ __global__ void k_maxks(RunsDesc R, uint32_t* out) {
     if (threadIdx.x == 0) atomicMax(out, smax);
 }
 
+/* Adds delta (mod 2^64) to the offset field of n index records, in place:
+ * one 8-byte load and one 8-byte store per record, the other 8 bytes of the
+ * record untouched. Serves both directions of a sliced compaction: -off_lo
+ * on a slice's uploaded input records, +base on output records about to
+ * leave. The records need no alignment (an input index follows its run's
+ * data bytes in the slab). */
+__global__ void k_index_rebase(uint8_t* index, uint64_t n, uint64_t delta) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += stride) {
+        uint8_t* rec = index + i * 16;
+        uint64_t off = ld_u64(rec) + delta;
+        __builtin_memcpy(rec, &off, 8);
+    }
+}
+
 struct dbeel_gpu_job {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -1643,11 +1664,20 @@ static int validate_runs(const dbeel_run_view* runs, size_t n_runs) {
  * stay valid (and padded like a slab) for the job's lifetime; nothing is
  * uploaded. Nothing in the pipeline needs one contiguous slab: k_emit
  * stores absolute source addresses, the pair table and the aux tier
- * depend only on counts and key sizes. */
+ * depend only on counts and key sizes.
+ *
+ * off_bias (may be NULL; not with borrowed): off_bias[r] is subtracted on
+ * the device from every index record offset of run r right after its index
+ * upload, before anything reads the records — the run view is a slice of a
+ * larger run whose records still carry offsets into the whole. A record
+ * that lies below the bias wraps to a huge offset, which load_entry's
+ * wrap-proof bounds test rejects (DBEEL_ERR_CORRUPT from job_run): that
+ * test is relied on, there is no second one. */
 static int job_create_impl(const dbeel_run_view* runs, size_t n_runs,
                            const uint32_t* runs_per_job, size_t n_jobs,
                            int device, dbeel_gpu_job** out_job,
-                           bool borrowed = false) {
+                           bool borrowed = false,
+                           const uint64_t* off_bias = nullptr) {
     g_err[0] = 0;
     if (!out_job) {
         set_err("out_job is null");
@@ -1757,6 +1787,11 @@ static int job_create_impl(const dbeel_run_view* runs, size_t n_runs,
         if (runs[r].index_len && !borrowed) {
             HIP_CHECK(hipMemcpyAsync(p, runs[r].index, runs[r].index_len,
                                      hipMemcpyHostToDevice, job->stream));
+            if (off_bias && off_bias[r])
+                hipLaunchKernelGGL(k_index_rebase,
+                                   dim3(pick_grid(D.count[r], 256)),
+                                   dim3(256), 0, job->stream, p, D.count[r],
+                                   (uint64_t)0 - off_bias[r]);
             p += runs[r].index_len;
         }
         D.entry_base[r] = base;
@@ -2532,6 +2567,112 @@ extern "C" int dbeel_gpu_job_fetch(dbeel_gpu_job* job,
     out->index_len = ilen;
     out->entries_written = job->out_entries;
     return DBEEL_OK;
+}
+
+/* Enqueues the copies of job's last result into data / index on the job's
+ * stream, between e0 and e1, and returns without waiting. The caps have
+ * been checked by the caller. With index_base != 0 the index records go
+ * through d_rank — dead between runs, 16 B per input entry, so never
+ * smaller than the output index — and are rebased there: d_outindex stays
+ * as job_run left it. */
+static int job_fetch_into_async(dbeel_gpu_job* job, uint8_t* data,
+                                uint8_t* index, uint64_t index_base,
+                                hipEvent_t e0, hipEvent_t e1) {
+    hipStream_t s = job->stream;
+    const uint64_t dlen = job->out_data_len, n = job->out_entries;
+    HIP_CHECK(hipEventRecord(e0, s));
+    const uint8_t* isrc = job->d_outindex;
+    if (n && index_base) {
+        uint8_t* scratch = (uint8_t*)job->d_rank;
+        HIP_CHECK(hipMemcpyAsync(scratch, job->d_outindex, n * 16,
+                                 hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL(k_index_rebase, dim3(pick_grid(n, 256)), dim3(256),
+                           0, s, scratch, n, index_base);
+        isrc = scratch;
+    }
+    if (dlen)
+        HIP_CHECK(hipMemcpyAsync(data, job->d_outdata, dlen,
+                                 hipMemcpyDeviceToHost, s));
+    if (n)
+        HIP_CHECK(hipMemcpyAsync(index, isrc, n * 16, hipMemcpyDeviceToHost,
+                                 s));
+    HIP_CHECK(hipEventRecord(e1, s));
+    return DBEEL_OK;
+}
+
+extern "C" int dbeel_gpu_job_fetch_into(
+    dbeel_gpu_job* job, uint8_t* data, uint64_t data_cap, uint8_t* index,
+    uint64_t index_cap, uint64_t index_base, uint64_t* data_len,
+    uint64_t* index_len, double* d2h_ms) {
+    g_err[0] = 0;
+    if (data_len) *data_len = 0;
+    if (index_len) *index_len = 0;
+    if (d2h_ms) *d2h_ms = 0;
+    if (!job || !data || !index || !data_len || !index_len) {
+        set_err("job_fetch_into: null argument");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (!job->have_result) {
+        set_err("job_fetch_into: no result available");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    const uint64_t dl = job->out_data_len, il = job->out_entries * 16;
+    *data_len = dl;
+    *index_len = il;
+    if (dl > data_cap || il > index_cap) {
+        set_err("job_fetch_into: output needs %llu data and %llu index "
+                "bytes, caps are %llu and %llu", (unsigned long long)dl,
+                (unsigned long long)il, (unsigned long long)data_cap,
+                (unsigned long long)index_cap);
+        return DBEEL_ERR_ITEM_TOO_LARGE;
+    }
+    hipStream_t s = job->stream;
+    ScopeGuard fail([&] { (void)hipStreamSynchronize(s); });
+    HIP_CHECK(hipSetDevice(job->device));
+    int rc = job_fetch_into_async(job, data, index, index_base, job->ev[0],
+                                  job->ev[1]);
+    if (rc) return rc;
+    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipGetLastError());
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, job->ev[0], job->ev[1]));
+    if (d2h_ms) *d2h_ms = ms;
+    fail.dismiss();
+    return DBEEL_OK;
+}
+
+/* The filter across slices: k_bloom_hash appends k_bloom's two hashes of
+ * every survivor of one job to hashes[2 * i], hashes[2 * i + 1]; k_bloom_fill
+ * sets k_bloom's bits from them once n_bits is known. */
+__global__ void k_bloom_hash(const uint8_t* out_data,
+                             const uint8_t* out_index, uint64_t n_surv,
+                             uint64_t seed, ulonglong2* hashes) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         i < n_surv; i += stride) {
+        const uint8_t* rec = out_index + i * 16;
+        uint64_t off = ld_u64(rec);
+        uint32_t key_size = ld_u32(rec + 8);
+        const uint8_t* key = out_data + off + 8;
+        uint64_t klen = key_size - 8;
+        ulonglong2 h;
+        h.x = d_fnv1a64(key, klen, seed);
+        h.y = d_fnv1a64(key, klen, seed ^ 0x9e3779b97f4a7c15ull) | 1;
+        hashes[i] = h;
+    }
+}
+
+__global__ void k_bloom_fill(const ulonglong2* hashes, uint64_t n,
+                             uint64_t n_bits, uint32_t kk, uint32_t* bits) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += stride) {
+        ulonglong2 h = hashes[i];
+        for (uint32_t j = 0; j < kk; j++) {
+            uint64_t bit = (h.x + j * h.y) % n_bits;
+            atomicOr(&bits[bit >> 5], 1u << (bit & 31));
+        }
+    }
 }
 
 /* ------------------------------------------------------------------ */
@@ -6971,6 +7112,316 @@ extern "C" int dbeel_gpu_compact_sliced(const dbeel_run_view* runs,
     out->data_len = acc_data.size();
     out->index_len = acc_index.size();
     out->entries_written = written;
+    return DBEEL_OK;
+}
+
+/* ------------------------------------------------------------------ */
+/* Compaction into caller buffers: slices pipelined, filter across     */
+/* slices. See include/dbeel_gpu.h.                                    */
+/* ------------------------------------------------------------------ */
+
+/* Grows the call's hash array to `need` bytes keeping its first `used`
+ * bytes; the copy and the free are ordered on s. */
+static int hashes_reserve(ulonglong2** p, uint64_t* cap, uint64_t used,
+                          uint64_t need, hipStream_t s) {
+    if (need <= *cap) return DBEEL_OK;
+    uint64_t want = need + need / 4;
+    ulonglong2* np = nullptr;
+    HIP_CHECK(hipMalloc(&np, want));
+    if (used) {
+        hipError_t e = hipMemcpyAsync(np, *p, used, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            (void)hipFree(np);
+            HIP_CHECK(e);
+        }
+    }
+    (void)hipFree(*p);
+    *p = np;
+    *cap = want;
+    return DBEEL_OK;
+}
+
+extern "C" int dbeel_gpu_compact_into(
+    const dbeel_run_view* runs, size_t n_runs, int keep_tombstones,
+    int device, uint64_t max_resident_bytes, uint32_t n_slices, uint8_t* data,
+    uint64_t data_cap, uint8_t* index, uint64_t index_cap, int want_bloom,
+    uint8_t** bloom_bytes, uint64_t* bloom_len,
+    dbeel_compact_into_result* result, dbeel_compact_into_stats* stats) {
+    g_err[0] = 0;
+    const auto t_begin = std::chrono::steady_clock::now();
+    if (!result) {
+        set_err("compact_into: result is null");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    memset(result, 0, sizeof *result);
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (bloom_bytes) *bloom_bytes = nullptr;
+    if (bloom_len) *bloom_len = 0;
+    if (!data || !index) {
+        set_err("compact_into: data or index is null");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (want_bloom && (!bloom_bytes || !bloom_len)) {
+        set_err("compact_into: want_bloom needs bloom_bytes and bloom_len");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (!runs || n_runs == 0 || n_runs > MAX_RUNS) {
+        set_err("compact_into: runs is null, empty or more than %d", MAX_RUNS);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    int rc = check_device_arg(device);
+    if (rc) return rc;
+    rc = validate_runs(runs, n_runs);
+    if (rc) return rc;
+
+    uint64_t total_input = 0, max_count = 0;
+    size_t big_run = 0;
+    for (size_t r = 0; r < n_runs; r++) {
+        total_input += runs[r].data_len + runs[r].index_len;
+        uint64_t c = runs[r].index_len / 16;
+        if (c > max_count) {
+            max_count = c;
+            big_run = r;
+        }
+    }
+    uint64_t S = n_slices;
+    if (!S) {
+        uint64_t budget = max_resident_bytes;
+        if (!budget) {
+            rc = select_device(device);
+            if (rc) return rc;
+            size_t free_b = 0, total_b = 0;
+            HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+            /* compact_sliced keeps one job under a third of free memory
+             * (~2.6x input per job); two jobs are alive here */
+            budget = (uint64_t)(free_b / 6);
+        }
+        S = budget ? (total_input + budget - 1) / budget : 1;
+    }
+    if (S > max_count / 2) S = max_count / 2;
+    if (S < 1) S = 1;
+
+    /* Slice boundaries, as compact_sliced finds them: pivots are evenly
+     * spaced keys of the largest run, bounds[r][sl] the first entry of run
+     * r not below pivot sl. cut[r][sl] is the data offset where slice sl
+     * of run r begins, read from the record AT the boundary; every record
+     * read here passes host_entry_key's bounds test first. */
+    std::vector<std::vector<uint64_t>> bounds(n_runs), cut(n_runs);
+    {
+        std::vector<std::pair<const uint8_t*, uint64_t>> pivots;
+        for (uint64_t j = 1; j < S; j++) {
+            uint64_t klen;
+            const uint8_t* k =
+                host_entry_key(&runs[big_run], j * max_count / S, &klen);
+            if (!k) {
+                set_err("corrupt index record in run %zu", big_run);
+                return DBEEL_ERR_CORRUPT;
+            }
+            pivots.push_back({k, klen});
+        }
+        for (size_t r = 0; r < n_runs; r++) {
+            const uint64_t n = runs[r].index_len / 16;
+            bounds[r].push_back(0);
+            cut[r].push_back(0);
+            for (auto& pv : pivots) {
+                uint64_t lo = bounds[r].back(), hi = n;
+                while (lo < hi) {
+                    uint64_t mid = (lo + hi) >> 1;
+                    uint64_t kl;
+                    const uint8_t* k = host_entry_key(&runs[r], mid, &kl);
+                    if (!k) {
+                        set_err("corrupt index record in run %zu", r);
+                        return DBEEL_ERR_CORRUPT;
+                    }
+                    if (host_key_cmp(k, kl, pv.first, pv.second) < 0)
+                        lo = mid + 1;
+                    else
+                        hi = mid;
+                }
+                uint64_t c = runs[r].data_len;
+                if (lo == 0) {
+                    c = 0;
+                } else if (lo < n) {
+                    uint64_t kl;
+                    if (!host_entry_key(&runs[r], lo, &kl)) {
+                        set_err("corrupt index record in run %zu", r);
+                        return DBEEL_ERR_CORRUPT;
+                    }
+                    c = ld_u64_host(runs[r].index + lo * 16);
+                }
+                if (c < cut[r].back()) {
+                    set_err("run %zu: index offsets not ascending", r);
+                    return DBEEL_ERR_CORRUPT;
+                }
+                bounds[r].push_back(lo);
+                cut[r].push_back(c);
+            }
+            bounds[r].push_back(n);
+            cut[r].push_back(runs[r].data_len);
+        }
+    }
+
+    rc = select_device(device);
+    if (rc) return rc;
+
+    dbeel_gpu_job* prev = nullptr; /* its fetch may be in flight */
+    bool prev_fetching = false;
+    hipEvent_t f0 = nullptr, f1 = nullptr;
+    hipStream_t bs = nullptr;      /* the call's own: the filter's fill */
+    ulonglong2* d_hashes = nullptr;
+    uint64_t hashes_cap = 0;
+    uint32_t* d_bits = nullptr;
+    ScopeGuard cleanup([&] {
+        if (prev) {
+            (void)hipStreamSynchronize(prev->stream);
+            dbeel_gpu_job_destroy(prev);
+        }
+        (void)hipFree(d_hashes);
+        (void)hipFree(d_bits);
+        if (f0) (void)hipEventDestroy(f0);
+        if (f1) (void)hipEventDestroy(f1);
+        if (bs) (void)hipStreamDestroy(bs);
+    });
+    HIP_CHECK(hipEventCreate(&f0));
+    HIP_CHECK(hipEventCreate(&f1));
+
+    dbeel_compact_into_stats st{};
+    uint64_t off_d = 0, off_i = 0, entries = 0;
+    bool short_caps = false;
+    float up_a = 0, up_b = 0; /* next upload's span, ms after prev's f0 */
+    bool up_valid = false;
+
+    /* waits for prev's copies, books their time and overlap, destroys it */
+    auto retire_prev = [&]() -> int {
+        if (!prev) return DBEEL_OK;
+        dbeel_gpu_job* j = prev;
+        prev = nullptr;
+        ScopeGuard drop([&] { dbeel_gpu_job_destroy(j); });
+        HIP_CHECK(hipStreamSynchronize(j->stream));
+        HIP_CHECK(hipGetLastError());
+        if (prev_fetching) {
+            float f = 0;
+            HIP_CHECK(hipEventElapsedTime(&f, f0, f1));
+            st.d2h_ms += f;
+            if (up_valid) {
+                float lo = up_a > 0 ? up_a : 0, hi = up_b < f ? up_b : f;
+                if (hi > lo) st.overlap_ms += hi - lo;
+            }
+        }
+        prev_fetching = false;
+        up_valid = false;
+        return DBEEL_OK;
+    };
+
+    std::vector<dbeel_run_view> views(n_runs);
+    std::vector<uint64_t> bias(n_runs);
+    const uint32_t one[1] = {(uint32_t)n_runs};
+    for (uint64_t sl = 0; sl < S; sl++) {
+        uint64_t slice_entries = 0, slice_bytes = 0;
+        for (size_t r = 0; r < n_runs; r++) {
+            const uint64_t lo = bounds[r][sl], hi = bounds[r][sl + 1];
+            const uint64_t c0 = cut[r][sl], c1 = cut[r][sl + 1];
+            /* an empty view keeps non-null pointers, as compact_sliced's */
+            views[r] = {runs[r].data + c0, hi > lo ? c1 - c0 : 0,
+                        runs[r].index + lo * 16, (hi - lo) * 16};
+            bias[r] = hi > lo ? c0 : 0;
+            slice_entries += hi - lo;
+            slice_bytes += views[r].data_len + views[r].index_len;
+        }
+        if (!slice_entries) continue;
+
+        dbeel_gpu_job* job = nullptr;
+        rc = job_create_impl(views.data(), n_runs, one, 1, device, &job,
+                             false, bias.data());
+        if (rc) return rc;
+        ScopeGuard drop_job([&] { dbeel_gpu_job_destroy(job); });
+        st.slices++;
+        st.bytes_in += slice_bytes;
+        st.h2d_ms += job->h2d_ms;
+        if (prev_fetching) {
+            /* job_create has waited for its own stream only: prev's copies
+             * went on meanwhile. ev[0] / ev[1] still bracket the upload. */
+            up_valid =
+                hipEventElapsedTime(&up_a, f0, job->ev[0]) == hipSuccess &&
+                hipEventElapsedTime(&up_b, f0, job->ev[1]) == hipSuccess;
+            (void)hipGetLastError();
+        }
+        uint64_t dl = 0, ne = 0;
+        dbeel_compact_timings tm{};
+        rc = dbeel_gpu_job_run(job, keep_tombstones, &dl, &ne, &tm);
+        if (rc) return rc;
+        st.kernel_ms += tm.kernel_ms;
+
+        /* the one wait per slice: after it no earlier job's stream holds
+         * work, so the hash array may move and the events may be reused */
+        rc = retire_prev();
+        if (rc) return rc;
+        if (off_d + dl > data_cap || off_i + ne * 16 > index_cap)
+            short_caps = true;
+        if (want_bloom && !short_caps && ne) {
+            rc = hashes_reserve(&d_hashes, &hashes_cap, entries * 16,
+                                (entries + ne) * 16, job->stream);
+            if (rc) return rc;
+            hipLaunchKernelGGL(k_bloom_hash, dim3(pick_grid(ne, 256)),
+                               dim3(256), 0, job->stream, job->d_outdata,
+                               job->d_outindex, ne, (uint64_t)BLOOM_SEED,
+                               d_hashes + entries);
+        }
+        if (!short_caps && ne) {
+            rc = job_fetch_into_async(job, data + off_d, index + off_i, off_d,
+                                      f0, f1);
+            if (rc) {
+                (void)hipStreamSynchronize(job->stream);
+                return rc;
+            }
+            prev_fetching = true;
+        }
+        off_d += dl;
+        off_i += ne * 16;
+        entries += ne;
+        drop_job.dismiss();
+        prev = job;
+    }
+    rc = retire_prev();
+    if (rc) return rc;
+
+    result->data_len = off_d;
+    result->index_len = off_i;
+    result->entries_written = entries;
+    st.bytes_out = off_d + off_i;
+    auto finish_stats = [&] {
+        st.wall_ms = std::chrono::duration<double, std::milli>(
+                         std::chrono::steady_clock::now() - t_begin).count();
+        if (stats) *stats = st;
+    };
+    if (short_caps) {
+        finish_stats();
+        set_err("compact_into: output needs %llu data and %llu index bytes, "
+                "caps are %llu and %llu", (unsigned long long)off_d,
+                (unsigned long long)off_i, (unsigned long long)data_cap,
+                (unsigned long long)index_cap);
+        return DBEEL_ERR_ITEM_TOO_LARGE;
+    }
+    if (want_bloom) {
+        /* every job's stream has been waited for: the hashes are complete */
+        const uint64_t n_bits = bloom_bits_for(entries);
+        const uint64_t n_words = (n_bits + 31) / 32;
+        HIP_CHECK(hipStreamCreate(&bs));
+        HIP_CHECK(hipMalloc(&d_bits, n_words * 4));
+        HIP_CHECK(hipMemsetAsync(d_bits, 0, n_words * 4, bs));
+        if (entries)
+            hipLaunchKernelGGL(k_bloom_fill, dim3(pick_grid(entries, 256)),
+                               dim3(256), 0, bs, d_hashes, entries, n_bits,
+                               BLOOM_K, d_bits);
+        ReaderTable t;
+        t.d_bits = (uint8_t*)d_bits;
+        t.bloom = {t.d_bits, n_bits, BLOOM_SEED, BLOOM_K, 0};
+        rc = table_bloom_fetch(t, bs, bloom_bytes, bloom_len);
+        if (rc) return rc;
+        HIP_CHECK(hipGetLastError());
+    }
+    finish_stats();
     return DBEEL_OK;
 }
 

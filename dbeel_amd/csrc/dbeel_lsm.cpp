@@ -396,6 +396,99 @@ extern "C" int dbeel_lsm_compact(const char* dir_c, const uint64_t* indices,
     return rc;
 }
 
+namespace {
+
+/* A host buffer page-locked for its lifetime (empty buffers stay unpinned:
+ * there is nothing to copy through them). */
+struct PinnedBuf {
+    std::vector<uint8_t> v;
+    bool pinned = false;
+    int pin() {
+        if (v.empty()) return DBEEL_OK;
+        int rc = dbeel_gpu_pin_host(v.data(), v.size());
+        pinned = rc == DBEEL_OK;
+        return rc;
+    }
+    ~PinnedBuf() {
+        if (pinned) dbeel_gpu_unpin_host(v.data());
+    }
+};
+
+} // namespace
+
+extern "C" int dbeel_lsm_compact_stream(const char* dir_c,
+                                        const uint64_t* indices,
+                                        size_t n_indices,
+                                        uint64_t output_index,
+                                        int keep_tombstones, int device,
+                                        uint64_t max_resident_bytes,
+                                        uint64_t sstable_bloom_min_size,
+                                        uint64_t* out_entries_written) {
+    if (!dir_c || !indices || n_indices == 0) return DBEEL_ERR_INVALID_ARG;
+    if (device < 0) {
+        /* nothing is pinned for a call the engine would refuse */
+        dbeel_set_last_error("lsm_compact_stream: device must be >= 0");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    std::string dir(dir_c);
+
+    std::vector<PinnedBuf> datas(n_indices), idxs(n_indices);
+    std::vector<dbeel_run_view> views(n_indices);
+    uint64_t total_input_data = 0, total_input_index = 0;
+    for (size_t i = 0; i < n_indices; i++) {
+        if (!read_whole(file_path(dir, indices[i], "data"), datas[i].v) ||
+            !read_whole(file_path(dir, indices[i], "index"), idxs[i].v))
+            return DBEEL_ERR_IO;
+        views[i] = {datas[i].v.data(), datas[i].v.size(), idxs[i].v.data(),
+                    idxs[i].v.size()};
+        total_input_data += datas[i].v.size();
+        total_input_index += idxs[i].v.size();
+    }
+    /* survivors are copied verbatim: the inputs' sums bound the output, so
+     * compact_into cannot refuse these caps. One byte extra keeps the
+     * pointers non-null for empty inputs. */
+    PinnedBuf out_data, out_index;
+    out_data.v.resize(total_input_data + 1);
+    out_index.v.resize(total_input_index + 1);
+    int rc = DBEEL_OK;
+    for (size_t i = 0; i < n_indices && rc == DBEEL_OK; i++) {
+        rc = datas[i].pin();
+        if (rc == DBEEL_OK) rc = idxs[i].pin();
+    }
+    if (rc == DBEEL_OK) rc = out_data.pin();
+    if (rc == DBEEL_OK) rc = out_index.pin();
+    if (rc != DBEEL_OK) return rc;
+
+    /* the same gate as dbeel_lsm_compact (lsm_tree.rs:1026-1034) */
+    bool with_bloom = total_input_data > sstable_bloom_min_size;
+    uint8_t* bloom = nullptr;
+    uint64_t bloom_len = 0;
+    dbeel_compact_into_result into{};
+    rc = dbeel_gpu_compact_into(views.data(), n_indices, keep_tombstones,
+                                device, max_resident_bytes, /*n_slices=*/0,
+                                out_data.v.data(), total_input_data,
+                                out_index.v.data(), total_input_index,
+                                with_bloom, &bloom, &bloom_len, &into,
+                                nullptr);
+    if (rc != DBEEL_OK) {
+        dbeel_gpu_bloom_free(bloom);
+        return rc;
+    }
+    dbeel_compact_result res{};
+    res.data = out_data.v.data();
+    res.data_len = into.data_len;
+    res.index = out_index.v.data();
+    res.index_len = into.index_len;
+    res.entries_written = into.entries_written;
+    rc = compact_file_half(dir, indices, n_indices, output_index, res,
+                           with_bloom ? bloom : nullptr, bloom_len, nullptr,
+                           nullptr);
+    if (rc == DBEEL_OK && out_entries_written)
+        *out_entries_written = into.entries_written;
+    dbeel_gpu_bloom_free(bloom);
+    return rc;
+}
+
 extern "C" int dbeel_lsm_major_compact(const char* dir_c, int device,
                                        uint64_t sstable_bloom_min_size,
                                        uint64_t* out_entries_written) {

@@ -293,6 +293,99 @@ def compact_sliced(runs, keep_tombstones: bool, device: int = 0,
     return data, index, n
 
 
+class CompactIntoResult(ctypes.Structure):
+    """dbeel_compact_into_result."""
+    _fields_ = [
+        ("data_len", ctypes.c_uint64),
+        ("index_len", ctypes.c_uint64),
+        ("entries_written", ctypes.c_uint64),
+    ]
+
+
+class CompactIntoStats(ctypes.Structure):
+    """dbeel_compact_into_stats."""
+    _fields_ = [
+        ("slices", ctypes.c_uint64),
+        ("bytes_in", ctypes.c_uint64),
+        ("bytes_out", ctypes.c_uint64),
+        ("h2d_ms", ctypes.c_double),
+        ("kernel_ms", ctypes.c_double),
+        ("d2h_ms", ctypes.c_double),
+        ("wall_ms", ctypes.c_double),
+        ("overlap_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def _load_into(lib):
+    if not hasattr(lib, "_into_ready"):
+        u8p = ctypes.POINTER(ctypes.c_uint8)
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        lib.dbeel_gpu_job_fetch_into.restype = ctypes.c_int
+        lib.dbeel_gpu_job_fetch_into.argtypes = [
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, u64p, u64p,
+            ctypes.POINTER(ctypes.c_double)]
+        lib.dbeel_gpu_compact_into.restype = ctypes.c_int
+        lib.dbeel_gpu_compact_into.argtypes = [
+            ctypes.POINTER(RunView), ctypes.c_size_t, ctypes.c_int,
+            ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32,
+            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+            ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(u8p), u64p,
+            ctypes.POINTER(CompactIntoResult),
+            ctypes.POINTER(CompactIntoStats)]
+        lib.dbeel_gpu_bloom_free.restype = None
+        lib.dbeel_gpu_bloom_free.argtypes = [u8p]
+        lib._into_ready = True
+    return lib
+
+
+def compact_into(runs, keep_tombstones: bool, data_arr: np.ndarray,
+                 index_arr: np.ndarray, device: int = 0,
+                 max_resident_bytes: int = 0, n_slices: int = 0,
+                 bloom: bool = False):
+    """dbeel_gpu_compact_into: compact runs [(data, index), ...] into the
+    caller's numpy u8 arrays (passed by pointer, so arrays registered with
+    pin_host receive true async DMA), in n_slices pipelined key slices
+    (0 = as many as max_resident_bytes / free device memory ask for). The
+    bytes written equal compact()'s.
+
+    Returns (data_len, index_len, entries_written, stats_dict, bloom_bytes);
+    bloom_bytes is the "DBLM" filter over the surviving keys, None unless
+    bloom. Arrays too small raise DbeelGpuError with code 3 and .needed =
+    (data_len, index_len); nothing past the arrays' ends is written."""
+    lib = _load_into(load())
+    views, keepalive = _views(runs)
+    res = CompactIntoResult()
+    st = CompactIntoStats()
+    bp = ctypes.POINTER(ctypes.c_uint8)()
+    bn = ctypes.c_uint64()
+    rc = lib.dbeel_gpu_compact_into(
+        views, len(runs), int(keep_tombstones), device,
+        int(max_resident_bytes), int(n_slices),
+        data_arr.ctypes.data, data_arr.nbytes,
+        index_arr.ctypes.data, index_arr.nbytes, int(bool(bloom)),
+        ctypes.byref(bp) if bloom else None,
+        ctypes.byref(bn) if bloom else None,
+        ctypes.byref(res), ctypes.byref(st))
+    del keepalive
+    if rc != 0:
+        err = DbeelGpuError(rc, lib.dbeel_gpu_last_error().decode())
+        err.needed = (int(res.data_len), int(res.index_len))
+        err.stats = st.as_dict()
+        raise err
+    bloom_bytes = None
+    if bloom:
+        try:
+            bloom_bytes = _ptr_bytes(bp, int(bn.value))
+        finally:
+            lib.dbeel_gpu_bloom_free(bp)
+    return (int(res.data_len), int(res.index_len), int(res.entries_written),
+            st.as_dict(), bloom_bytes)
+
+
 class LookupHit(ctypes.Structure):
     _fields_ = [
         ("run", ctypes.c_int32),
@@ -1630,6 +1723,28 @@ class Job:
         finally:
             self._lib.dbeel_gpu_result_free(ctypes.byref(res))
         return data, index, n
+
+    def fetch_into(self, data_arr: np.ndarray, index_arr: np.ndarray,
+                   index_base: int = 0):
+        """fetch() into the caller's numpy u8 arrays (by pointer: pinned
+        arrays receive true async DMA), every index record's offset leaving
+        with index_base added on the device; the job's own result is not
+        changed by it. Returns (data_len, index_len, d2h_ms). Arrays too
+        small raise DbeelGpuError with code 3 and .needed = (data_len,
+        index_len), and nothing is written."""
+        lib = _load_into(self._lib)
+        dl = ctypes.c_uint64()
+        il = ctypes.c_uint64()
+        ms = ctypes.c_double()
+        rc = lib.dbeel_gpu_job_fetch_into(
+            self._h, data_arr.ctypes.data, data_arr.nbytes,
+            index_arr.ctypes.data, index_arr.nbytes, int(index_base),
+            ctypes.byref(dl), ctypes.byref(il), ctypes.byref(ms))
+        if rc != 0:
+            err = DbeelGpuError(rc, lib.dbeel_gpu_last_error().decode())
+            err.needed = (int(dl.value), int(il.value))
+            raise err
+        return int(dl.value), int(il.value), float(ms.value)
 
     def bloom(self) -> bytes:
         """The "DBLM" filter over the last run()'s surviving keys, built

@@ -62,6 +62,33 @@ def compact(dir: str, indices, output_index: int, keep_tombstones: bool,
     return int(out.value)
 
 
+def compact_stream(dir: str, indices, output_index: int,
+                   keep_tombstones: bool, device: int = 0,
+                   max_resident_bytes: int = 0,
+                   bloom_min_size: int = DEFAULT_BLOOM_MIN_SIZE) -> int:
+    """compact() for inputs of any size (dbeel_lsm_compact_stream): pinned
+    buffers, pipelined key slices of at most max_resident_bytes of input
+    (0 = from free device memory), the filter built across slices. Leaves
+    the directory byte-identical to compact()'s."""
+    lib = load()
+    if not hasattr(lib, "_lsm_stream_ready"):
+        lib.dbeel_lsm_compact_stream.restype = ctypes.c_int
+        lib.dbeel_lsm_compact_stream.argtypes = [
+            ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t,
+            ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
+            ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
+        ]
+        lib._lsm_stream_ready = True
+    arr = (ctypes.c_uint64 * len(indices))(*indices)
+    out = ctypes.c_uint64()
+    rc = lib.dbeel_lsm_compact_stream(
+        dir.encode(), arr, len(indices), output_index, int(keep_tombstones),
+        device, int(max_resident_bytes), bloom_min_size, ctypes.byref(out),
+    )
+    _check(rc, lib)
+    return int(out.value)
+
+
 def replay(dir: str) -> int:
     lib = load()
     n = ctypes.c_uint32()

@@ -943,6 +943,111 @@ int dbeel_gpu_compact_sliced(const dbeel_run_view* runs, size_t n_runs,
                              uint64_t max_resident_bytes,
                              dbeel_compact_result* out);
 
+/* ---- Compaction into caller buffers: pipelined slices, bloom across
+ * slices ----
+ *
+ * job_fetch_into: dbeel_gpu_job_fetch into caller memory. The last run's
+ * .data and .index bytes are copied with hipMemcpyAsync on the job's stream
+ * (true async DMA when the buffers are registered with dbeel_gpu_pin_host);
+ * no host memory is allocated. Every index record's offset leaves with
+ * index_base added — the place of this output inside a larger file. The
+ * addition runs ON THE DEVICE and INTO SCRATCH: with index_base != 0 the
+ * records are copied device-to-device into a buffer of the job that is dead
+ * between runs (the rank records) and rebased there by k_index_rebase, so
+ * the job's own output index is never modified and a later job_fetch,
+ * job_fetch_job, job_bloom or another fetch_into sees the un-rebased result.
+ * *data_len / *index_len receive the output's sizes, d2h_ms (may be NULL)
+ * the copies' time. A NULL argument other than d2h_ms, or a job without a
+ * result: DBEEL_ERR_INVALID_ARG (lengths zeroed). A cap too small:
+ * DBEEL_ERR_ITEM_TOO_LARGE with *data_len / *index_len set to what is
+ * needed and nothing written to the buffers. */
+int dbeel_gpu_job_fetch_into(dbeel_gpu_job* job,
+        uint8_t* data, uint64_t data_cap, uint8_t* index, uint64_t index_cap,
+        uint64_t index_base, uint64_t* data_len, uint64_t* index_len,
+        double* d2h_ms /* may be NULL */);
+
+/* compact_into: dbeel_gpu_compact with the output written into the caller's
+ * data / index buffers — byte-identical to dbeel_gpu_compact for the same
+ * runs, whatever the slice count. The key space is cut into S slices at
+ * strict key pivots (dbeel_gpu_compact_sliced's: evenly spaced keys of the
+ * largest run, so an equal-key group never splits); each slice is an
+ * ordinary job, and slice i's output travels to the host while slice i+1's
+ * input travels to the device:
+ *
+ *   create job i (upload) -> run -> start its fetch at the running output
+ *   offsets -> WITHOUT waiting, create + run job i+1 -> wait for job i's
+ *   copies, destroy it -> start job i+1's fetch -> ...
+ *
+ * Two jobs are alive at once. A slice with no input entries is skipped; a
+ * slice with no survivors moves no offsets. One slice is a legal outcome
+ * and goes through the same code.
+ *
+ * S: n_slices > 0 asks for that many. n_slices == 0 uses
+ * dbeel_gpu_compact_sliced's budget rule, S = ceil(input bytes / budget),
+ * budget = max_resident_bytes, or with max_resident_bytes == 0 a SIXTH of
+ * the device's free memory (half of compact_sliced's third, because two jobs
+ * are alive). Either way S is capped so that the largest run has at least
+ * two entries per slice (S <= max_count / 2, at least 1).
+ *
+ * No per-entry host loop: a slice's input index records are uploaded as
+ * they are and a device pass (k_index_rebase) subtracts the slice's first
+ * data offset; the output records get the running output offset added by
+ * the same kernel (see job_fetch_into). A record of a slice that points
+ * below the slice's first byte wraps to a huge offset and is refused by the
+ * entry loader's bounds test like any other corrupt record
+ * (DBEEL_ERR_CORRUPT from the slice's run).
+ *
+ * Caps: a caller that sizes data at the sum of the runs' data_len and index
+ * at the sum of their index_len can never be refused (survivors are copied
+ * verbatim). When the output does not fit, the call keeps running the
+ * remaining slices without copying and returns DBEEL_ERR_ITEM_TOO_LARGE with
+ * the exact sizes needed in *result; bytes inside the caps are then
+ * unspecified, bytes past the caps are never touched, and no filter is
+ * returned.
+ *
+ * Bloom: with want_bloom != 0 (bloom_bytes and bloom_len both required;
+ * free with dbeel_gpu_bloom_free) the "DBLM" filter over all surviving keys
+ * is built across slices: per slice k_bloom_hash appends the two 64-bit
+ * hashes of every survivor to a device array owned by the call (16 B per
+ * survivor, grown geometrically), and once the total survivor count — and
+ * with it n_bits — is known, k_bloom_fill sets the bits. The bytes equal
+ * dbeel_gpu_job_bloom's on the whole job. With want_bloom == 0 neither
+ * kernel is launched.
+ *
+ * Validated on the host before any device call, in this order: NULL result
+ * (then *result, *stats and the bloom outputs are zeroed), NULL data or
+ * index, want_bloom with a NULL bloom_bytes or bloom_len, NULL runs /
+ * n_runs == 0 / n_runs > 64 (DBEEL_ERR_INVALID_ARG); device < 0
+ * (DBEEL_ERR_INVALID_ARG); a bad run view (dbeel_gpu_job_create's codes);
+ * then, when S > 1, a corrupt index record met during pivot selection
+ * (DBEEL_ERR_CORRUPT). With n_slices == 0 and max_resident_bytes == 0 the
+ * free-memory query precedes pivot selection.
+ *
+ * stats (may be NULL), all from HIP events and host clocks — nothing is
+ * counted on the device: slices = jobs actually run; bytes_in = input bytes
+ * uploaded; bytes_out = data + index bytes of the output; h2d_ms /
+ * kernel_ms / d2h_ms = sums over slices; wall_ms = the whole call;
+ * overlap_ms = summed time during which a slice's upload and the previous
+ * slice's fetch were both in flight. */
+typedef struct {
+    uint64_t data_len;        /* output .data bytes (needed, when refused) */
+    uint64_t index_len;       /* output .index bytes (needed, when refused) */
+    uint64_t entries_written;
+} dbeel_compact_into_result;
+
+typedef struct {
+    uint64_t slices, bytes_in, bytes_out;
+    double   h2d_ms, kernel_ms, d2h_ms, wall_ms, overlap_ms;
+} dbeel_compact_into_stats;
+
+int dbeel_gpu_compact_into(const dbeel_run_view* runs, size_t n_runs,
+        int keep_tombstones, int device, uint64_t max_resident_bytes,
+        uint32_t n_slices,
+        uint8_t* data, uint64_t data_cap, uint8_t* index, uint64_t index_cap,
+        int want_bloom, uint8_t** bloom_bytes, uint64_t* bloom_len,
+        dbeel_compact_into_result* result,
+        dbeel_compact_into_stats* stats /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

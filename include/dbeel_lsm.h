@@ -39,6 +39,26 @@ int dbeel_lsm_compact(const char* dir, const uint64_t* indices,
                       uint64_t sstable_bloom_min_size,
                       uint64_t* out_entries_written);
 
+/* dbeel_lsm_compact for inputs of any size: same contract, same staging
+ * files, journal, crash hook (DBEEL_LSM_CRASH_AFTER_JOURNAL), renames and
+ * deletes — the directory ends byte-identical to dbeel_lsm_compact's, the
+ * .bloom included — but the device half is dbeel_gpu_compact_into
+ * (include/dbeel_gpu.h): the inputs are read into buffers this call
+ * page-locks, the output is fetched into page-locked buffers sized at the
+ * inputs' summed lengths (which bound it, so the fetch cannot be refused),
+ * slices are pipelined, and the filter — gated by
+ * total input data > sstable_bloom_min_size exactly as above — is built
+ * across slices. max_resident_bytes bounds one slice's input (0 = from the
+ * device's free memory); inputs that fit run as one slice. Everything is
+ * unpinned before the call returns. device < 0 is DBEEL_ERR_INVALID_ARG
+ * before any file is read. */
+int dbeel_lsm_compact_stream(const char* dir, const uint64_t* indices,
+                             size_t n_indices, uint64_t output_index,
+                             int keep_tombstones, int device,
+                             uint64_t max_resident_bytes,
+                             uint64_t sstable_bloom_min_size,
+                             uint64_t* out_entries_written);
+
 /* Replay any {n:020}.compact_action journals in dir: per journal, deletes
  * first (if present), then renames (if source present), then remove the
  * journal — idempotent compaction completion after a crash

@@ -5,7 +5,8 @@ Draws random run-set shapes (run count, entry counts incl. empty runs,
 key/value size distributions incl. ragged and zero-length, timestamp
 ranges incl. negatives and collisions, overlap patterns) and checks the
 HIP engine's output is bit-identical to the CPU oracle for both
-keep_tombstones settings. Heavier than the pytest suite — run via gpurun:
+keep_tombstones settings; every trial also runs compact_into at a random
+slice count against compact(). Heavier than the pytest suite:
 
     python tools/fuzz_parity.py --trials 150 --seed 1
 """
@@ -385,6 +386,31 @@ def live_reader_step(rng, rd, runs, blooms, queries, device):
     return differs(what)
 
 
+def compact_into_step(rng, runs, keep, want, device):
+    """compact_into at a random slice count (forced, or through a random
+    budget), with and without the filter, against compact()'s result and
+    the whole job's filter. Returns a mismatch description or None."""
+    from dbeel_amd.engine import Job, compact_into
+
+    data = np.empty(sum(len(d) for d, _ in runs) + 1, dtype=np.uint8)
+    index = np.empty(sum(len(i) for _, i in runs) + 1, dtype=np.uint8)
+    total = len(data) + len(index)
+    kw = ({"n_slices": int(rng.integers(1, 20))} if rng.random() < 0.7
+          else {"max_resident_bytes": int(rng.integers(1, total + 1))})
+    bloom = bool(rng.integers(0, 2))
+    dl, il, n, st, gb = compact_into(runs, keep, data, index, device=device,
+                                     bloom=bloom, **kw)
+    got = (data[:dl].tobytes(), index[:il].tobytes(), n)
+    if got != tuple(want):
+        return f"{kw}: n {n} vs {want[2]} in {st['slices']} slices"
+    if bloom:
+        with Job(runs, device=device) as job:
+            job.run(keep)
+            if job.bloom() != gb:
+                return f"{kw}: filter differs from the whole job's"
+    return None
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--trials", type=int, default=100)
@@ -408,6 +434,8 @@ def main():
     for t in range(args.trials):
         rng = np.random.default_rng(args.seed * 1_000_003 + t)
         runs = random_runs(rng)
+        # its own stream: the draws of the older steps stay what they were
+        srng = np.random.default_rng([args.seed, t, 0x51])
         for keep in (True, False):
             od, oi, on = oracle.compact(runs, keep_tombstones=keep)
             gd, gi, gn = dbeel_amd.compact(runs, keep_tombstones=keep,
@@ -416,6 +444,11 @@ def main():
                 failures += 1
                 print(f"TRIAL {t} keep={keep} MISMATCH: "
                       f"n {gn} vs {on}, index {gi == oi}, data {gd == od}")
+            why = compact_into_step(srng, runs, keep, (gd, gi, gn),
+                                    args.device)
+            if why:
+                failures += 1
+                print(f"TRIAL {t} keep={keep} COMPACT_INTO MISMATCH: {why}")
         if args.scan:
             kw = random_scan_filter(rng)
             sd, si, sn = gpu_scan(runs, device=args.device, **kw)

@@ -12,7 +12,9 @@ after a flush / snapshot scans begun, paged and ended across an insert, two
 puts and a compaction, one left for close / close with a non-empty
 memtable / put_entries of a host page, a refused corrupt page, scan_apply
 into a second reader with deletes back into the source, flushes, close with
-that scan open), reporting hipMemGetInfo drift. A leak in any path shows as monotonically shrinking free memory.
+that scan open) and compact_into (1 and several slices, pinned and pageable
+destinations, with and without the filter, a refused short cap, a job's
+fetch_into), reporting hipMemGetInfo drift. A leak in any path shows as monotonically shrinking free memory.
 
     python tools/leakcheck.py --iters 40
 """
@@ -31,6 +33,7 @@ from dbeel_amd.engine import (  # noqa: E402
     DbeelGpuError,
     Job,
     Reader,
+    compact_into,
     compact_sliced,
     flush_batch,
     load,
@@ -240,6 +243,25 @@ def main():
                 dst.memtable_flush(fetch=False)
                 src.memtable_flush(fetch=False)
                 # close ends mig and frees what it holds
+            # compact_into: jobs, events, the hash array and the filter
+            # bitmap are the call's; pinned (data) and pageable (index)
+            # destinations, 1 and several slices, with and without the
+            # filter, and a refused short cap that still runs every slice
+            for n_slices, bloom in ((1, False), (1, True), (5, True),
+                                    (9, False)):
+                compact_into(runs, False, fetch_d, fetch_i, device=0,
+                             n_slices=n_slices, bloom=bloom)
+            compact_into(runs, True, fetch_d, fetch_i, device=0,
+                         max_resident_bytes=total_in // 3, bloom=True)
+            try:
+                compact_into(runs, True, fetch_d[:4096], fetch_i, device=0,
+                             n_slices=4, bloom=True)
+                raise SystemExit("compact_into accepted a short buffer")
+            except DbeelGpuError:
+                pass
+            with Job(runs, device=0) as job:
+                job.run(False)
+                job.fetch_into(fetch_d, fetch_i, index_base=1 << 33)
             flush_batch(batch[:7000], device=0)
             f = free_mem()
             if base is None:
