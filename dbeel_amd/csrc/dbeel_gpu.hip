@@ -3152,6 +3152,12 @@ struct dbeel_gpu_reader {
     uint8_t* d_values = nullptr;
     uint64_t values_cap = 0;
     unsigned long long* d_stats = nullptr;
+    /* get_merged, when this reader is the local one: candidates, winners,
+     * offsets, merge hits and totals; the uploaded answers */
+    uint8_t* d_merge = nullptr;
+    uint64_t merge_cap = 0;
+    uint8_t* d_answers = nullptr;
+    uint64_t answers_cap = 0;
     /* paged scans: generation is bumped by every edit of the table list
      * (a scan from an older generation is stale); the per-page scratch, the
      * device page buffer and the copy's window map grow on demand and are
@@ -3291,6 +3297,8 @@ extern "C" void dbeel_gpu_reader_close(dbeel_gpu_reader* rd) {
     (void)hipFree(rd->d_scantmp);
     (void)hipFree(rd->d_values);
     (void)hipFree(rd->d_stats);
+    (void)hipFree(rd->d_merge);
+    (void)hipFree(rd->d_answers);
     (void)hipFree(rd->d_scan);
     (void)hipFree(rd->d_page);
     (void)hipFree(rd->d_scanwin);
@@ -5609,6 +5617,519 @@ extern "C" int dbeel_gpu_reader_get_entries(
     if (n_done == 0) { /* n > 0: record 0 alone is over the cap */
         set_err("reader_get_entries: record 0 needs %llu bytes, "
                 "records_cap is %llu", (unsigned long long)page->needed,
+                (unsigned long long)buf->records_cap);
+        return DBEEL_ERR_ITEM_TOO_LARGE;
+    }
+    return DBEEL_OK;
+}
+
+/* ------------------------------------------------------------------ */
+/* get_merged: the replicated read (tasks/db_server.rs:338-363)       */
+/*                                                                    */
+/* The reference collects the replicas' Option<EntryValue> answers,   */
+/* pushes the local one last, takes max_by_key(timestamp) and only    */
+/* then tests for a tombstone. Here every candidate — another reader  */
+/* on this device, or a replica's get_entries answer uploaded from    */
+/* the host — is reduced to one {address, length} per query, the      */
+/* newest is picked per query on the device, and only the winners'    */
+/* records are gathered and leave the device.                         */
+/*                                                                    */
+/*   k_reader_search : per reader candidate, launched as get_entries  */
+/*                     launches it (a source reader on its own stream */
+/*                     into its own scratch).                         */
+/*   k_merge_stage   : one launch per candidate: hit records or       */
+/*                     answer offsets -> cand[candidate][query];      */
+/*                     uploaded records are validated here.           */
+/*   k_merge_pick    : thread per query: newest timestamp, ties to    */
+/*                     the later candidate, stale mask, counters.     */
+/*   rocPRIM scan    : winner lengths -> exclusive record offsets.    */
+/*   k_merge_page    : the paging rule on the device, so the offsets  */
+/*                     reach the caller only once the call is known   */
+/*                     to succeed.                                    */
+/*   k_merge_gather  : wave per delivered query, from the winner's    */
+/*                     absolute address.                              */
+/* ------------------------------------------------------------------ */
+
+/* One candidate's answer to one query; len == 0 = absent. */
+struct MergeCand {
+    const uint8_t* rec;
+    uint64_t len;
+};
+static_assert(sizeof(MergeCand) == 16, "cand entries are 16 B");
+
+struct CandLen {
+    __device__ uint64_t operator()(const MergeCand& c) const { return c.len; }
+};
+
+enum { MS_WINNERS, MS_TOMBS, MS_LOCAL, MS_N };
+#define MERGE_NO_ERR 0xFFFFFFFFFFFFFFFFull
+
+/* What k_merge_page leaves for the host's one mid-call read: the counters,
+ * the first corrupt answer as source << 32 | query (MERGE_NO_ERR = none;
+ * atomicMin keeps the lowest) and the page. */
+struct MergeTotals {
+    unsigned long long stats[MS_N];
+    unsigned long long err;
+    dbeel_get_page page;
+};
+
+/* hits != NULL: a reader candidate, its hit records resolved through its own
+ * descriptor and memtable (k_reader_gather_entries' addressing). Otherwise an
+ * uploaded answer: rec_off / rec are its n + 1 offsets and record bytes on
+ * the device. The host has checked that the offsets ascend from 0, so every
+ * range lies inside the upload; a record that cannot be an EntryValue
+ * (shorter than 24 bytes, or a data_len that is not its size - 24) is
+ * reported and staged as absent. */
+__global__ void k_merge_stage(RunsDesc R, const uint8_t* mem_data,
+                              const dbeel_lookup_hit* hits,
+                              const uint64_t* rec_off, const uint8_t* rec,
+                              uint64_t n, uint32_t source, MergeCand* out,
+                              unsigned long long* err) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n;
+         q += stride) {
+        MergeCand c = {nullptr, 0};
+        if (hits) {
+            const dbeel_lookup_hit h = hits[q];
+            if (h.run >= 0) {
+                const uint8_t* src =
+                    h.run >= R.n_runs ? mem_data : R.data[h.run];
+                c.rec = src + h.value_offset - 8;
+                c.len = h.value_len + 24;
+            }
+        } else {
+            const uint64_t o = rec_off[q], len = rec_off[q + 1] - o;
+            if (len) {
+                if (len < 24 || ld_u64(rec + o) != len - 24) {
+                    atomicMin(err, ((unsigned long long)source << 32) | q);
+                } else {
+                    c.rec = rec + o;
+                    c.len = len;
+                }
+            }
+        }
+        out[q] = c;
+    }
+}
+
+/* cand is [n_cand][n]: a wave reads 64 consecutive entries of one candidate.
+ * The timestamp is the record's last 16 bytes, i128 little-endian, loaded as
+ * bytes (records are byte-aligned at best) and compared as a signed high
+ * half, then an unsigned low half. `tied` holds the candidates equal to the
+ * best so far, so one pass yields the stale mask: a newer candidate makes
+ * all of them stale, an older one is stale itself, and the winner is the
+ * highest tied index (max_by_key returns the last maximum). */
+__global__ __launch_bounds__(256) void k_merge_pick(
+    const MergeCand* cand, uint32_t n_cand, uint64_t n, dbeel_merge_hit* hits,
+    MergeCand* win, unsigned long long* stats) {
+    __shared__ unsigned long long s_stats[MS_N];
+    if (threadIdx.x < MS_N) s_stats[threadIdx.x] = 0;
+    __syncthreads();
+    unsigned long long cnt[MS_N] = {};
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n;
+         q += stride) {
+        MergeCand best = {nullptr, 0};
+        int64_t bhi = 0;
+        uint64_t blo = 0;
+        uint32_t tied = 0, stale = 0, absent = 0;
+        for (uint32_t c = 0; c < n_cand; c++) {
+            const MergeCand m = cand[(uint64_t)c * n + q];
+            if (!m.len) {
+                absent |= 1u << c;
+                continue;
+            }
+            const uint64_t lo = ld_u64(m.rec + m.len - 16);
+            const int64_t hi = (int64_t)ld_u64(m.rec + m.len - 8);
+            if (tied && (hi < bhi || (hi == bhi && lo < blo))) {
+                stale |= 1u << c;
+                continue;
+            }
+            if (tied && hi == bhi && lo == blo) {
+                tied |= 1u << c;
+            } else {
+                stale |= tied;
+                tied = 1u << c;
+                bhi = hi;
+                blo = lo;
+            }
+            best = m;
+        }
+        dbeel_merge_hit h;
+        h.source = tied ? 31 - __clz((int)tied) : -1;
+        h.is_tombstone = best.len == 24 ? 1 : 0;
+        h.value_len = best.len ? best.len - 24 : 0;
+        h.stale_mask = tied ? (uint64_t)(stale | absent) : 0;
+        hits[q] = h;
+        win[q] = best;
+        if (tied) {
+            cnt[MS_WINNERS]++;
+            if (best.len == 24) cnt[MS_TOMBS]++;
+            if (h.source == (int32_t)n_cand - 1) cnt[MS_LOCAL]++;
+        }
+    }
+    #pragma unroll
+    for (int s = 0; s < MS_N; s++)
+        if (cnt[s]) atomicAdd(&s_stats[s], cnt[s]);
+    __syncthreads();
+    if (threadIdx.x < MS_N && s_stats[threadIdx.x])
+        atomicAdd(&stats[threadIdx.x], s_stats[threadIdx.x]);
+}
+
+/* get_entries' paging rule on the n + 1 ascending offsets: n_done is the
+ * largest d with off[d] <= cap, and exactly one d in [0, n] has
+ * off[d] <= cap with d == n or off[d + 1] > cap (off[0] = 0 always fits). */
+__global__ void k_merge_page(const uint64_t* off, uint64_t n, uint64_t cap,
+                             dbeel_get_page* page) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t d = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; d <= n;
+         d += stride) {
+        if (off[d] > cap || (d < n && off[d + 1] <= cap)) continue;
+        page->n_done = d;
+        page->records_len = off[d];
+        page->records_total = off[n];
+        page->needed = d < n ? off[d + 1] - off[d] : 0;
+    }
+}
+
+/* One wave per delivered query copies the winner's record verbatim, reading
+ * exactly the record and writing exactly the record. */
+__global__ void k_merge_gather(const MergeCand* win, const uint64_t* rec_off,
+                               uint64_t n_done, uint8_t* records) {
+    uint32_t lane = threadIdx.x & 63;
+    uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    for (uint64_t q = wave; q < n_done; q += n_waves) {
+        const MergeCand w = win[q];
+        if (!w.len) continue;
+        wave_copy_bytes(records + rec_off[q], w.rec, w.len, lane);
+    }
+}
+
+static inline uint64_t round8(uint64_t x) { return (x + 7) & ~7ull; }
+
+extern "C" int dbeel_gpu_reader_get_merged(
+    dbeel_gpu_reader* rd, const uint8_t* keys, const uint64_t* key_offsets,
+    uint64_t n_keys, const dbeel_merge_source* sources, size_t n_sources,
+    const dbeel_merge_buffers* buf, dbeel_get_page* page,
+    dbeel_merge_stats* stats) {
+    g_err[0] = 0;
+    const char* who = "reader_get_merged";
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (page) memset(page, 0, sizeof *page);
+    if (!rd || !buf || !page) {
+        set_err("%s: null reader, buf or page", who);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (n_keys &&
+        (!keys || !key_offsets || !buf->hits || !buf->record_offsets)) {
+        set_err("%s: null keys, key_offsets, hits or record_offsets", who);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (!buf->records && buf->records_cap) {
+        set_err("%s: null records with records_cap %llu", who,
+                (unsigned long long)buf->records_cap);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (n_keys >= (1ull << 32)) {
+        set_err("%s: 2^32 or more keys in one batch", who);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    for (uint64_t i = 0; i < n_keys; i++)
+        if (key_offsets[i + 1] < key_offsets[i]) {
+            set_err("%s: key_offsets not ascending at %llu", who,
+                    (unsigned long long)i);
+            return DBEEL_ERR_INVALID_ARG;
+        }
+    if (n_sources > DBEEL_MERGE_MAX_SOURCES) {
+        set_err("%s: %zu sources, at most %d", who, n_sources,
+                DBEEL_MERGE_MAX_SOURCES);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    if (n_sources && !sources) {
+        set_err("%s: null sources with n_sources %zu", who, n_sources);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    for (size_t i = 0; i < n_sources; i++)
+        if (sources[i].kind != DBEEL_MERGE_ANSWERS &&
+            sources[i].kind != DBEEL_MERGE_READER) {
+            set_err("%s: source %zu has unknown kind %d", who, i,
+                    sources[i].kind);
+            return DBEEL_ERR_INVALID_ARG;
+        }
+    for (size_t i = 0; i < n_sources; i++) {
+        if (sources[i].kind != DBEEL_MERGE_READER) continue;
+        const dbeel_gpu_reader* sr = sources[i].reader;
+        if (!sr) {
+            set_err("%s: source %zu has no reader", who, i);
+            return DBEEL_ERR_INVALID_ARG;
+        }
+        if (sr == rd) {
+            set_err("%s: source %zu is the local reader itself", who, i);
+            return DBEEL_ERR_INVALID_ARG;
+        }
+        if (sr->device != rd->device) {
+            set_err("%s: source %zu's reader is on device %d, the local one "
+                    "on device %d", who, i, sr->device, rd->device);
+            return DBEEL_ERR_INVALID_ARG;
+        }
+    }
+    for (size_t i = 0; i < n_sources; i++) {
+        if (sources[i].kind != DBEEL_MERGE_ANSWERS) continue;
+        if (!sources[i].record_offsets) {
+            set_err("%s: source %zu has null record_offsets", who, i);
+            return DBEEL_ERR_INVALID_ARG;
+        }
+        if (!sources[i].records && sources[i].record_offsets[n_keys]) {
+            set_err("%s: source %zu has null records with %llu record bytes",
+                    who, i,
+                    (unsigned long long)sources[i].record_offsets[n_keys]);
+            return DBEEL_ERR_INVALID_ARG;
+        }
+    }
+    for (size_t i = 0; i < n_sources; i++) {
+        if (sources[i].kind != DBEEL_MERGE_ANSWERS) continue;
+        const uint64_t* o = sources[i].record_offsets;
+        if (o[0] != 0) {
+            set_err("%s: source %zu's record_offsets start at %llu, not 0",
+                    who, i, (unsigned long long)o[0]);
+            return DBEEL_ERR_INVALID_ARG;
+        }
+        for (uint64_t q = 0; q < n_keys; q++)
+            if (o[q + 1] < o[q]) {
+                set_err("%s: source %zu's record_offsets not ascending at "
+                        "%llu", who, i, (unsigned long long)q);
+                return DBEEL_ERR_INVALID_ARG;
+            }
+    }
+    const uint64_t n = n_keys;
+    if (n == 0) {
+        if (buf->record_offsets) buf->record_offsets[0] = 0;
+        return DBEEL_OK;
+    }
+
+    const uint32_t n_cand = (uint32_t)n_sources + 1;
+    const uint64_t kbytes = key_offsets[n];
+    const uint64_t off_bytes = (n + 1) * sizeof(uint64_t);
+    /* the uploaded answers, each as offsets | records, 8-B aligned */
+    uint64_t ans_bytes = 0;
+    for (size_t i = 0; i < n_sources; i++)
+        if (sources[i].kind == DBEEL_MERGE_ANSWERS)
+            ans_bytes += off_bytes + round8(sources[i].record_offsets[n]);
+    /* d_merge layout: cand (n_cand * n) | winners (n + 1, the last one absent
+     * so the scan's final element is the total) | record offsets (n + 1) |
+     * merge hits (n) | totals */
+    const uint64_t cand_bytes = (uint64_t)n_cand * n * sizeof(MergeCand);
+    const uint64_t merge_bytes = cand_bytes + (n + 1) * sizeof(MergeCand) +
+                                 off_bytes + n * sizeof(dbeel_merge_hit) +
+                                 sizeof(MergeTotals);
+    size_t tmp_bytes = 0;
+    MergeTotals tot;
+    float ms[7] = {};
+    double search_ms = 0;
+    hipStream_t s = rd->stream;
+    /* on failure nothing of this batch may still be in flight into the
+     * caller's buffers or out of a source's scratch */
+    ScopeGuard fail([&] {
+        (void)hipStreamSynchronize(s);
+        for (size_t i = 0; i < n_sources; i++)
+            if (sources[i].kind == DBEEL_MERGE_READER)
+                (void)hipStreamSynchronize(sources[i].reader->stream);
+    });
+
+    HIP_CHECK(hipSetDevice(rd->device));
+    HIP_CHECK(reader_reserve((void**)&rd->d_keys, &rd->keys_cap,
+                             kbytes ? kbytes : 1));
+    /* d_batch as get_entries lays it out; its record-offset slot is unused */
+    HIP_CHECK(reader_reserve((void**)&rd->d_batch, &rd->batch_cap,
+                             2 * off_bytes +
+                                 (n + 1) * sizeof(dbeel_lookup_hit)));
+    HIP_CHECK(reader_reserve((void**)&rd->d_merge, &rd->merge_cap,
+                             merge_bytes));
+    HIP_CHECK(reader_reserve((void**)&rd->d_answers, &rd->answers_cap,
+                             ans_bytes ? ans_bytes : 1));
+    for (size_t i = 0; i < n_sources; i++)
+        if (sources[i].kind == DBEEL_MERGE_READER) {
+            dbeel_gpu_reader* sr = sources[i].reader;
+            HIP_CHECK(reader_reserve((void**)&sr->d_batch, &sr->batch_cap,
+                                     n * sizeof(dbeel_lookup_hit)));
+        }
+    uint64_t* d_koff = (uint64_t*)rd->d_batch;
+    dbeel_lookup_hit* d_hits = (dbeel_lookup_hit*)(d_koff + 2 * (n + 1));
+    MergeCand* d_cand = (MergeCand*)rd->d_merge;
+    MergeCand* d_win = d_cand + (uint64_t)n_cand * n;
+    uint64_t* d_roff = (uint64_t*)(d_win + (n + 1));
+    dbeel_merge_hit* d_mhits = (dbeel_merge_hit*)(d_roff + (n + 1));
+    MergeTotals* d_tot = (MergeTotals*)(d_mhits + n);
+    HIP_CHECK(rocprim::exclusive_scan(
+        nullptr, tmp_bytes,
+        rocprim::make_transform_iterator(d_win, CandLen{}), d_roff,
+        (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), s));
+    HIP_CHECK(reader_reserve(&rd->d_scantmp, &rd->scantmp_cap,
+                             tmp_bytes ? tmp_bytes : 1));
+
+    HIP_CHECK(hipEventRecord(rd->ev[0], s));
+    if (kbytes)
+        HIP_CHECK(hipMemcpyAsync(rd->d_keys, keys, kbytes,
+                                 hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_koff, key_offsets, off_bytes,
+                             hipMemcpyHostToDevice, s));
+    uint64_t ans_at = 0;
+    for (size_t i = 0; i < n_sources; i++) {
+        if (sources[i].kind != DBEEL_MERGE_ANSWERS) continue;
+        const uint64_t rb = sources[i].record_offsets[n];
+        HIP_CHECK(hipMemcpyAsync(rd->d_answers + ans_at,
+                                 sources[i].record_offsets, off_bytes,
+                                 hipMemcpyHostToDevice, s));
+        if (rb)
+            HIP_CHECK(hipMemcpyAsync(rd->d_answers + ans_at + off_bytes,
+                                     sources[i].records, rb,
+                                     hipMemcpyHostToDevice, s));
+        ans_at += off_bytes + round8(rb);
+    }
+    HIP_CHECK(hipMemsetAsync(rd->d_stats, 0, RS_N * sizeof(uint64_t), s));
+    HIP_CHECK(hipMemsetAsync(d_tot, 0, sizeof *d_tot, s));
+    HIP_CHECK(hipMemsetAsync(&d_tot->err, 0xFF, sizeof d_tot->err, s));
+    HIP_CHECK(hipMemsetAsync(d_win + n, 0, sizeof(MergeCand), s));
+    HIP_CHECK(hipEventRecord(rd->ev[1], s));
+
+    /* every reader candidate is searched as get_entries searches it; a
+     * source on its own stream, once the keys are up, into its own scratch */
+    typedef void (*SearchFn)(RunsDesc, ReaderPfx, ReaderMem,
+                             const ReaderBloom*, const uint8_t*,
+                             const uint64_t*, uint64_t, dbeel_lookup_hit*,
+                             unsigned long long*);
+    for (size_t i = 0; i < n_sources; i++) {
+        if (sources[i].kind != DBEEL_MERGE_READER) continue;
+        dbeel_gpu_reader* sr = sources[i].reader;
+        HIP_CHECK(hipStreamWaitEvent(sr->stream, rd->ev[1], 0));
+        HIP_CHECK(hipMemsetAsync(sr->d_stats, 0, RS_N * sizeof(uint64_t),
+                                 sr->stream));
+        HIP_CHECK(hipEventRecord(sr->ev[0], sr->stream));
+        SearchFn ks = k_reader_search<false>;
+        if (sr->mem.count) ks = k_reader_search<true>;
+        hipLaunchKernelGGL(ks, dim3(pick_grid(n, READER_BLOCK)),
+                           dim3(READER_BLOCK), 0, sr->stream, sr->desc,
+                           sr->pfx, sr->mem.view(), sr->d_blooms, rd->d_keys,
+                           d_koff, n, (dbeel_lookup_hit*)sr->d_batch,
+                           sr->d_stats);
+        HIP_CHECK(hipEventRecord(sr->ev[1], sr->stream));
+    }
+    {
+        SearchFn ks = k_reader_search<false>;
+        if (rd->mem.count) ks = k_reader_search<true>;
+        hipLaunchKernelGGL(ks, dim3(pick_grid(n, READER_BLOCK)),
+                           dim3(READER_BLOCK), 0, s, rd->desc, rd->pfx,
+                           rd->mem.view(), rd->d_blooms, rd->d_keys, d_koff,
+                           n, d_hits, rd->d_stats);
+    }
+    HIP_CHECK(hipEventRecord(rd->ev[2], s));
+    /* a source's hit records are read on the local stream: its own stream
+     * is drained first */
+    for (size_t i = 0; i < n_sources; i++) {
+        if (sources[i].kind != DBEEL_MERGE_READER) continue;
+        dbeel_gpu_reader* sr = sources[i].reader;
+        HIP_CHECK(hipStreamSynchronize(sr->stream));
+        float t = 0;
+        HIP_CHECK(hipEventElapsedTime(&t, sr->ev[0], sr->ev[1]));
+        search_ms += t;
+    }
+    HIP_CHECK(hipGetLastError());
+
+    HIP_CHECK(hipEventRecord(rd->ev[6], s));
+    const dim3 grid_n(pick_grid(n, 256)), block(256);
+    ans_at = 0;
+    for (uint32_t c = 0; c < n_cand; c++) {
+        MergeCand* out = d_cand + (uint64_t)c * n;
+        if (c == n_sources) {
+            hipLaunchKernelGGL(k_merge_stage, grid_n, block, 0, s, rd->desc,
+                               rd->mem.view().data, d_hits, nullptr, nullptr,
+                               n, c, out, &d_tot->err);
+        } else if (sources[c].kind == DBEEL_MERGE_READER) {
+            const dbeel_gpu_reader* sr = sources[c].reader;
+            hipLaunchKernelGGL(k_merge_stage, grid_n, block, 0, s, sr->desc,
+                               sr->mem.view().data,
+                               (const dbeel_lookup_hit*)sr->d_batch, nullptr,
+                               nullptr, n, c, out, &d_tot->err);
+        } else {
+            const uint8_t* a = rd->d_answers + ans_at;
+            hipLaunchKernelGGL(k_merge_stage, grid_n, block, 0, s, RunsDesc{},
+                               nullptr, nullptr, (const uint64_t*)a,
+                               a + off_bytes, n, c, out, &d_tot->err);
+            ans_at += off_bytes + round8(sources[c].record_offsets[n]);
+        }
+    }
+    hipLaunchKernelGGL(k_merge_pick, grid_n, block, 0, s, d_cand, n_cand, n,
+                       d_mhits, d_win, d_tot->stats);
+    HIP_CHECK(hipEventRecord(rd->ev[3], s));
+    HIP_CHECK(rocprim::exclusive_scan(
+        rd->d_scantmp, tmp_bytes,
+        rocprim::make_transform_iterator(d_win, CandLen{}), d_roff,
+        (uint64_t)0, n + 1, rocprim::plus<uint64_t>(), s));
+    hipLaunchKernelGGL(k_merge_page, dim3(pick_grid(n + 1, 256)), block, 0, s,
+                       d_roff, n, buf->records_cap, &d_tot->page);
+    HIP_CHECK(hipEventRecord(rd->ev[4], s));
+    /* the one mid-call read: counters, error word and page. The caller's
+     * buffers are written only after the error word is known to be clear. */
+    HIP_CHECK(hipMemcpyAsync(&tot, d_tot, sizeof tot, hipMemcpyDeviceToHost,
+                             s));
+    HIP_CHECK(hipEventRecord(rd->ev[5], s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventElapsedTime(&ms[0], rd->ev[0], rd->ev[1]));
+    HIP_CHECK(hipEventElapsedTime(&ms[1], rd->ev[1], rd->ev[2]));
+    HIP_CHECK(hipEventElapsedTime(&ms[2], rd->ev[6], rd->ev[3]));
+    HIP_CHECK(hipEventElapsedTime(&ms[3], rd->ev[3], rd->ev[4]));
+    HIP_CHECK(hipEventElapsedTime(&ms[4], rd->ev[4], rd->ev[5]));
+    if (tot.err != MERGE_NO_ERR) {
+        fail.dismiss(); /* every stream is idle */
+        set_err("%s: source %llu's answer to query %llu is not an "
+                "EntryValue record (shorter than 24 bytes, or its data_len "
+                "is not its size - 24)", who, tot.err >> 32,
+                tot.err & 0xFFFFFFFFull);
+        return DBEEL_ERR_CORRUPT;
+    }
+    *page = tot.page;
+    const uint64_t n_done = page->n_done, len = page->records_len;
+
+    if (len)
+        HIP_CHECK(reader_reserve((void**)&rd->d_values, &rd->values_cap,
+                                 len));
+    HIP_CHECK(hipEventRecord(rd->ev[4], s));
+    if (len)
+        hipLaunchKernelGGL(k_merge_gather,
+                           dim3(pick_grid(n_done * 64, 256)), block, 0, s,
+                           d_win, d_roff, n_done, rd->d_values);
+    HIP_CHECK(hipEventRecord(rd->ev[5], s));
+    /* hits and offsets go out complete whatever the cap */
+    HIP_CHECK(hipMemcpyAsync(buf->record_offsets, d_roff, off_bytes,
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(buf->hits, d_mhits, n * sizeof *buf->hits,
+                             hipMemcpyDeviceToHost, s));
+    if (len)
+        HIP_CHECK(hipMemcpyAsync(buf->records, rd->d_values, len,
+                                 hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipEventRecord(rd->ev[6], s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventElapsedTime(&ms[5], rd->ev[4], rd->ev[5]));
+    HIP_CHECK(hipEventElapsedTime(&ms[6], rd->ev[5], rd->ev[6]));
+    if (stats) {
+        stats->h2d_ms = ms[0];
+        stats->search_ms = ms[1] + search_ms; /* the search kernels' own
+                                                 times; sources overlap the
+                                                 local one                */
+        stats->pick_ms = ms[2];               /* stage launches + pick    */
+        stats->gather_ms = ms[3] + ms[5];     /* scan, page, gather       */
+        stats->d2h_ms = ms[4] + ms[6];        /* every copy to the host   */
+        stats->winners = tot.stats[MS_WINNERS];
+        stats->tombstones = tot.stats[MS_TOMBS];
+        stats->from_local = tot.stats[MS_LOCAL];
+    }
+    fail.dismiss();
+    if (n_done == 0) { /* n > 0: record 0 alone is over the cap */
+        set_err("%s: record 0 needs %llu bytes, records_cap is %llu", who,
+                (unsigned long long)page->needed,
                 (unsigned long long)buf->records_cap);
         return DBEEL_ERR_ITEM_TOO_LARGE;
     }

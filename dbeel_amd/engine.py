@@ -541,6 +541,65 @@ class GetPage(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+MERGE_ANSWERS = 0   # DBEEL_MERGE_ANSWERS
+MERGE_READER = 1    # DBEEL_MERGE_READER
+MERGE_MAX_SOURCES = 15
+
+
+class MergeSource(ctypes.Structure):
+    """dbeel_merge_source."""
+    _fields_ = [
+        ("kind", ctypes.c_int),
+        ("reader", ctypes.c_void_p),
+        ("record_offsets", ctypes.POINTER(ctypes.c_uint64)),
+        ("records", ctypes.POINTER(ctypes.c_uint8)),
+    ]
+
+
+class MergeHit(ctypes.Structure):
+    """dbeel_merge_hit."""
+    _fields_ = [
+        ("source", ctypes.c_int32),
+        ("is_tombstone", ctypes.c_uint32),
+        ("value_len", ctypes.c_uint64),
+        ("stale_mask", ctypes.c_uint64),
+    ]
+
+
+MERGE_HIT_DTYPE = np.dtype(
+    [("source", "<i4"), ("is_tombstone", "<u4"), ("value_len", "<u8"),
+     ("stale_mask", "<u8")]
+)
+assert MERGE_HIT_DTYPE.itemsize == ctypes.sizeof(MergeHit)
+
+
+class MergeBuffers(ctypes.Structure):
+    """dbeel_merge_buffers: all caller-owned."""
+    _fields_ = [
+        ("hits", ctypes.POINTER(MergeHit)),
+        ("record_offsets", ctypes.POINTER(ctypes.c_uint64)),
+        ("records", ctypes.POINTER(ctypes.c_uint8)),
+        ("records_cap", ctypes.c_uint64),
+    ]
+
+
+class MergeStats(ctypes.Structure):
+    """dbeel_merge_stats."""
+    _fields_ = [
+        ("h2d_ms", ctypes.c_double),
+        ("search_ms", ctypes.c_double),
+        ("pick_ms", ctypes.c_double),
+        ("gather_ms", ctypes.c_double),
+        ("d2h_ms", ctypes.c_double),
+        ("winners", ctypes.c_uint64),
+        ("tombstones", ctypes.c_uint64),
+        ("from_local", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class ReaderCompactStats(ctypes.Structure):
     _fields_ = [
         ("pipeline", CompactTimings),
@@ -791,6 +850,12 @@ def _load_reader() -> ctypes.CDLL:
             ctypes.c_void_p, _U8P, _U64P, ctypes.c_uint64,
             ctypes.POINTER(GetBuffers), ctypes.POINTER(GetPage),
             ctypes.POINTER(GetStats)]
+        lib.dbeel_gpu_reader_get_merged.restype = ctypes.c_int
+        lib.dbeel_gpu_reader_get_merged.argtypes = [
+            ctypes.c_void_p, _U8P, _U64P, ctypes.c_uint64,
+            ctypes.POINTER(MergeSource), ctypes.c_size_t,
+            ctypes.POINTER(MergeBuffers), ctypes.POINTER(GetPage),
+            ctypes.POINTER(MergeStats)]
         lib.dbeel_gpu_reader_put_entries.restype = ctypes.c_int
         lib.dbeel_gpu_reader_put_entries.argtypes = [
             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
@@ -1356,6 +1421,21 @@ class Reader:
             ctypes.byref(buf), ctypes.byref(page), ctypes.byref(st))
         return rc, page, st
 
+    @staticmethod
+    def _records_arg(records, records_cap):
+        """The records / records_cap arguments of get_entries_raw and
+        get_merged_raw -> (u8 array, cap)."""
+        if records is None:
+            cap = (64 << 20) if records_cap is None else int(records_cap)
+            return np.empty(max(cap, 1), dtype=np.uint8), cap
+        if (records.dtype != np.uint8 or records.ndim != 1
+                or not records.flags.c_contiguous):
+            raise ValueError("records must be a contiguous 1-D uint8 array")
+        cap = records.size if records_cap is None else int(records_cap)
+        if cap > records.size:
+            raise ValueError("records_cap exceeds the records array")
+        return records, cap
+
     def get_entries_raw(self, keys, records=None, records_cap=None):
         """get_entry for a batch, with timestamps: -> (hits HIT_DTYPE array,
         record_offsets u64[n+1], records view, page dict, stats dict). The
@@ -1374,17 +1454,7 @@ class Reader:
         and .record_offsets, which are complete."""
         ka, koff = _key_blob(keys)
         n = len(keys)
-        if records is None:
-            cap = (64 << 20) if records_cap is None else int(records_cap)
-            records = np.empty(max(cap, 1), dtype=np.uint8)
-        else:
-            if (records.dtype != np.uint8 or records.ndim != 1
-                    or not records.flags.c_contiguous):
-                raise ValueError("records must be a contiguous 1-D uint8 "
-                                 "array")
-            cap = records.size if records_cap is None else int(records_cap)
-            if cap > records.size:
-                raise ValueError("records_cap exceeds the records array")
+        records, cap = self._records_arg(records, records_cap)
         hits = np.empty(n, dtype=HIT_DTYPE)
         roff = np.zeros(n + 1, dtype=np.uint64)
         rc, page, st = self._get_entries_into(ka, koff, hits, roff, records,
@@ -1430,6 +1500,144 @@ class Reader:
                 out.append((rec[8:-16],
                             int.from_bytes(rec[-16:], "little", signed=True)))
         return out
+
+    @staticmethod
+    def _merge_sources(sources):
+        """sources — each a Reader or a (record_offsets, records) pair as
+        get_entries_raw returns them — as a dbeel_merge_source array:
+        -> (array or None, keepalive)."""
+        sources = list(sources)
+        if not sources:
+            return None, []
+        arr = (MergeSource * len(sources))()
+        keep = []
+        for i, s in enumerate(sources):
+            if isinstance(s, Reader):
+                if not s._h:
+                    raise ValueError("source reader is closed")
+                arr[i].kind = MERGE_READER
+                arr[i].reader = s._h
+                keep.append(s)
+                continue
+            off, rec = s
+            off = np.ascontiguousarray(off, dtype=np.uint64)
+            if rec is None:  # legal when the answer holds no record bytes
+                rec = np.zeros(0, dtype=np.uint8)
+            rec = (np.frombuffer(rec, dtype=np.uint8)
+                   if isinstance(rec, (bytes, bytearray))
+                   else np.ascontiguousarray(rec, dtype=np.uint8))
+            arr[i].kind = MERGE_ANSWERS
+            arr[i].record_offsets = off.ctypes.data_as(_U64P)
+            if rec.size:
+                arr[i].records = rec.ctypes.data_as(_U8P)
+            keep += [off, rec]
+        return arr, keep
+
+    def _get_merged_into(self, ka, koff, srcs, n_sources, hits, roff,
+                         records, cap):
+        """dbeel_gpu_reader_get_merged over the key blob ka / offsets koff
+        and the dbeel_merge_source array srcs into the caller's arrays: hits
+        (MERGE_HIT_DTYPE, n), roff (u64, n + 1), records (u8, at least cap
+        bytes, or None with cap 0). -> (rc, GetPage, MergeStats); nothing is
+        raised."""
+        if not self._h:
+            raise ValueError("reader is closed")
+        n = len(koff) - 1
+        buf = MergeBuffers(
+            hits.ctypes.data_as(ctypes.POINTER(MergeHit)),
+            roff.ctypes.data_as(_U64P),
+            None if records is None else records.ctypes.data_as(_U8P),
+            cap)
+        page = GetPage()
+        st = MergeStats()
+        rc = self._lib.dbeel_gpu_reader_get_merged(
+            self._h, ka.ctypes.data_as(_U8P), koff.ctypes.data_as(_U64P), n,
+            srcs, n_sources, ctypes.byref(buf), ctypes.byref(page),
+            ctypes.byref(st))
+        return rc, page, st
+
+    def get_merged_raw(self, keys, sources, records=None, records_cap=None):
+        """The replicated read's pick for a batch (tasks/db_server.rs:
+        338-363): -> (hits MERGE_HIT_DTYPE array, record_offsets u64[n+1],
+        records view, page dict, stats dict). The candidates of a key are
+        the sources' answers in order and this reader's own LAST; the winner
+        has the greatest timestamp, the highest index among equals. A source
+        is a Reader on the same device or a (record_offsets, records) pair
+        as get_entries_raw returns them for the same keys. hits["source"]
+        names the winner (len(sources) = this reader, -1 = nobody holds the
+        key), hits["stale_mask"] the candidates that are absent or older.
+        Records, buffers, paging and the error protocol are
+        get_entries_raw's; for the next page the caller advances the keys
+        and every pair (offsets rebased to 0)."""
+        ka, koff = _key_blob(keys)
+        n = len(keys)
+        records, cap = self._records_arg(records, records_cap)
+        srcs, keep = self._merge_sources(sources)
+        hits = np.empty(n, dtype=MERGE_HIT_DTYPE)
+        roff = np.zeros(n + 1, dtype=np.uint64)
+        rc, page, st = self._get_merged_into(
+            ka, koff, srcs, len(srcs) if srcs is not None else 0, hits, roff,
+            records, cap)
+        del keep
+        if rc != 0:
+            err = DbeelGpuError(rc, self._lib.dbeel_gpu_last_error().decode())
+            err.page, err.hits, err.record_offsets = page.as_dict(), hits, roff
+            raise err
+        return (hits, roff, records[:int(page.records_len)], page.as_dict(),
+                st.as_dict())
+
+    def get_merged(self, keys, sources, page_bytes: int = 64 << 20):
+        """The newest answer across replicas for a batch: a list of None
+        (no candidate holds the key) or (data: bytes, timestamp: int,
+        source: int), a winning tombstone being (b"", ts, source). Pages
+        like get_entries; the (record_offsets, records) sources are sliced
+        per page."""
+        keys = list(keys)
+        sources = [s if isinstance(s, Reader)
+                   else (np.ascontiguousarray(s[0], dtype=np.uint64),
+                         np.frombuffer(s[1], dtype=np.uint8)
+                         if isinstance(s[1], (bytes, bytearray))
+                         else np.ascontiguousarray(s[1], dtype=np.uint8))
+                   for s in sources]
+        records = np.empty(max(int(page_bytes), 1), dtype=np.uint8)
+        cap = int(page_bytes)
+        out = []
+        grown = False
+        while len(out) < len(keys):
+            p = len(out)
+            page_src = [s if isinstance(s, Reader)
+                        else (s[0][p:] - s[0][p],
+                              s[1][int(s[0][p]):int(s[0][-1])])
+                        for s in sources]
+            try:
+                hits, roff, view, page, _ = self.get_merged_raw(
+                    keys[p:], page_src, records=records, records_cap=cap)
+            except DbeelGpuError as e:
+                if e.code != 3 or grown:
+                    raise
+                cap = int(e.page["needed"])
+                records = np.empty(cap, dtype=np.uint8)
+                grown = True
+                continue
+            grown = False
+            blob = view.tobytes()
+            off = roff.tolist()
+            for q, s in enumerate(hits["source"][:page["n_done"]].tolist()):
+                if s < 0:
+                    out.append(None)
+                    continue
+                rec = blob[off[q]:off[q + 1]]
+                out.append((rec[8:-16],
+                            int.from_bytes(rec[-16:], "little", signed=True),
+                            s))
+        return out
+
+    def get_replicated(self, keys, sources, page_bytes: int = 64 << 20):
+        """The client-facing answer of a replicated get (db_server.rs:
+        355-363): the newest candidate's data, or None when nobody holds the
+        key or the newest answer is a tombstone."""
+        return [None if m is None or not m[0] else m[0]
+                for m in self.get_merged(keys, sources, page_bytes)]
 
     def compact_fetch_into(self, data_arr, index_arr):
         """Copy the PENDING compaction output's .data / .index bytes — what

@@ -290,6 +290,122 @@ int dbeel_gpu_reader_get_entries(dbeel_gpu_reader* reader,
         const dbeel_get_buffers* buf, dbeel_get_page* page,
         dbeel_get_stats* stats /* may be NULL */);
 
+/* ---- get_merged: replicated reads, the newest answer across replicas ----
+ * The reference's replicated get (tasks/db_server.rs:338-363) collects the
+ * remote replicas' Option<EntryValue> answers, pushes the local one last,
+ * takes max_by_key(timestamp) and only then tests for a tombstone. This call
+ * does that for a batch on the device: the local reader's answer and up to
+ * DBEEL_MERGE_MAX_SOURCES other answers per query go in, only the winners'
+ * records come out, in get_entries' record format, caller buffers and paging.
+ *
+ * Candidates, in order: sources[0] .. sources[n_sources-1], then the local
+ * reader LAST, as candidate n_sources (the reference pushes local_value
+ * last). A READER candidate answers exactly as get_entries on that reader
+ * would (memtable first, reported at run == n_runs, then the tables newest
+ * index first, filters consulted as there). An ANSWERS candidate answers
+ * query q with records[record_offsets[q] .. record_offsets[q+1]), an empty
+ * range meaning absent — the pair a replica's get_entries delivers.
+ *
+ * Winner: the candidate with the greatest timestamp, the record's last 16
+ * bytes as i128 little-endian (a signed high half, then an unsigned low
+ * half). Among equal timestamps the HIGHEST candidate index wins — Rust's
+ * max_by_key returns the last maximum, so the local answer wins a tie with a
+ * remote one. Absent candidates are skipped (flatten). With no candidate
+ * holding the key, source = -1 and the record range is empty. A winning
+ * tombstone is a 24-byte record with is_tombstone = 1; the client-facing
+ * "not found" decision (db_server.rs:361) stays with the caller.
+ *
+ * stale_mask: bit s is set iff a winner exists and candidate s is absent or
+ * strictly older than the winner (an equal timestamp is not stale); without
+ * a winner it is 0. It is what read repair needs; no repair is applied here.
+ *
+ * Records: the winner's record, copied verbatim from its table, memtable or
+ * uploaded answer. record_offsets covers all keys; hits and record_offsets
+ * are always delivered complete; page (n_done, records_len, records_total,
+ * needed) follows get_entries' rule word for word, DBEEL_ERR_ITEM_TOO_LARGE
+ * for a first record over the cap included. No byte of records at or beyond
+ * records_len is written, and no element beyond hits[n_keys-1] or
+ * record_offsets[n_keys]. The call is stateless: the next page is a new call
+ * with the remaining keys and every ANSWERS source advanced by the caller
+ * (offsets rebased to 0). n_keys == 0 succeeds as in get_entries.
+ *
+ * n_sources == 0 is legal: record_offsets and records are then byte-identical
+ * to get_entries' for the same keys and cap, and every found key has
+ * source == 0.
+ *
+ * Validated on the host before any device call, page and stats zeroed first,
+ * in this order, each DBEEL_ERR_INVALID_ARG:
+ *   1. a NULL local reader, buf or page;
+ *   2. get_entries' own key and buffer checks, in its order;
+ *   3. n_sources > DBEEL_MERGE_MAX_SOURCES, or NULL sources with
+ *      n_sources > 0;
+ *   4. a source of unknown kind;
+ *   5. a READER source with a NULL reader, with the local reader itself, or
+ *      with a reader on another device;
+ *   6. an ANSWERS source with NULL record_offsets, or with NULL records while
+ *      record_offsets[n_keys] > 0;
+ *   7. an ANSWERS source whose offsets do not start at 0 or do not ascend.
+ *
+ * Remote bytes are untrusted: an ANSWERS record that is non-empty and shorter
+ * than 24 bytes, or whose leading data_len differs from its size - 24, makes
+ * the call DBEEL_ERR_CORRUPT. This is found on the device; the message names
+ * the source and the query (the lowest of each), and nothing has then been
+ * written to any caller buffer. On every failure all readers are as they
+ * were.
+ *
+ * Memory and streams: no host allocation for results, nothing registered by
+ * the engine. ANSWERS sources go up with hipMemcpyAsync on the local reader's
+ * stream (true async DMA when registered with dbeel_gpu_pin_host). Scratch is
+ * reader-owned, grown on demand and reused; none of it counts in table_bytes.
+ * A READER source is searched on its own stream into its own scratch, after
+ * the keys are up, and that stream is synchronised before the local stream
+ * reads its hit records (scan_apply's ordering). The paging rule runs on the
+ * device, so one small mid-call read brings back the page, the counters and
+ * the error word, and the caller's buffers are written only after that; a
+ * final sync ends the call.
+ *
+ * stats: search_ms sums the search kernels' own times over all reader
+ * candidates (sources overlap the local search in wall time); pick_ms is the
+ * per-candidate staging plus the pick; gather_ms the offset scan, the page
+ * rule and the record gather; d2h_ms every copy to the host. winners counts
+ * queries with a winner, tombstones the winners that are tombstones,
+ * from_local the winners that are the local answer. */
+#define DBEEL_MERGE_ANSWERS 0   /* a replica's get_entries answer, host memory   */
+#define DBEEL_MERGE_READER  1   /* another reader on the same device             */
+#define DBEEL_MERGE_MAX_SOURCES 15
+
+typedef struct {
+    int kind;
+    dbeel_gpu_reader* reader;        /* READER                                    */
+    const uint64_t* record_offsets;  /* ANSWERS: n_keys + 1, as get_entries gives */
+    const uint8_t*  records;         /* ANSWERS: record_offsets[n_keys] bytes     */
+} dbeel_merge_source;
+
+typedef struct {
+    int32_t  source;        /* winner: 0..n_sources-1, n_sources = local, -1 none */
+    uint32_t is_tombstone;  /* winner's data is empty                             */
+    uint64_t value_len;     /* winner's data bytes; its record is 24 + value_len  */
+    uint64_t stale_mask;    /* bit s: candidate s is absent or older than winner  */
+} dbeel_merge_hit;
+
+typedef struct {
+    dbeel_merge_hit* hits;            /* n_keys                                   */
+    uint64_t*        record_offsets;  /* n_keys + 1, exclusive                    */
+    uint8_t*         records;         /* records_cap bytes; NULL iff cap == 0     */
+    uint64_t         records_cap;
+} dbeel_merge_buffers;                /* all caller-owned, never freed here       */
+
+typedef struct {
+    double   h2d_ms, search_ms, pick_ms, gather_ms, d2h_ms;
+    uint64_t winners, tombstones, from_local;
+} dbeel_merge_stats;
+
+int dbeel_gpu_reader_get_merged(dbeel_gpu_reader* local,
+        const uint8_t* keys, const uint64_t* key_offsets, uint64_t n_keys,
+        const dbeel_merge_source* sources, size_t n_sources,
+        const dbeel_merge_buffers* buf, dbeel_get_page* page,
+        dbeel_merge_stats* stats /* may be NULL */);
+
 /* ---- Live reader: the shared sstable list ----
  * The reference's LSMTree keeps one list of open sstables that reads,
  * flushes and compactions share: a flush pushes the new table

@@ -99,12 +99,13 @@ def random_scan_filter(rng):
     return kw
 
 
-def reader_trial(rng, runs, device):
+def reader_trial(rng, runs, device, mrng):
     """Resident reader vs the host model of the reference read path
     (highest run index wins, b"" = deleted, None = absent), with the
     engine's own filters on a random subset of the runs. Queries: stored
-    keys, their one-byte mutations and extensions, and random keys.
-    Returns a mismatch description or None."""
+    keys, their one-byte mutations and extensions, and random keys. mrng is
+    the get_merged step's own stream, so the other steps' draws stay what
+    they were. Returns a mismatch description or None."""
     from dbeel_amd import lsm
     from dbeel_amd.engine import Job, Reader
     from dbeel_amd.format import parse_run
@@ -143,6 +144,7 @@ def reader_trial(rng, runs, device):
         got = rd.get(queries)
         _, _, _, st = rd.get_raw(queries)
         scan_why = (get_entries_step(rng, rd, runs, queries)
+                    or get_merged_step(mrng, rd, runs, queries, device)
                     or paged_scan_step(rng, rd, runs, stored)
                     or migrate_step(rng, rd, runs, device))
         if got == exp and not scan_why:
@@ -198,6 +200,84 @@ def get_entries_step(rng, rd, runs, queries):
     page_bytes = int(rng.integers(0, 4096))
     if rd.get_entries(queries, page_bytes=page_bytes) != model.entries(queries):
         return f"get_entries page_bytes {page_bytes}: entries differ"
+    return None
+
+
+MERGED = {"calls": 0, "sources": 0}  # what the get_merged step compared
+
+
+def get_merged_step(rng, rd, runs, queries, device):
+    """get_merged of the open reader against tests/merge_model: 0..4 random
+    sources — readers and answer pairs over random subsets of the reader's
+    own runs (equal timestamps, so ties) and over fresh random runs drawn
+    from the stored keys with random timestamps — one call at a random cap
+    (hits, offsets, page and delivered bytes), then the paging loop."""
+    sys.path.insert(0, os.path.join(
+        os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import get_entries_model as gem
+    import merge_model as mm
+    from dbeel_amd.engine import MERGE_HIT_DTYPE, DbeelGpuError, Reader
+    from dbeel_amd.format import parse_run
+
+    stored = [e for d, i in runs for e in parse_run(d, i)]
+    local = gem.Model(runs)
+    readers, sources, msources = [], [], []
+    try:
+        for _ in range(int(rng.integers(0, 5))):
+            if rng.random() < 0.5 or not stored:
+                k = int(rng.integers(1, len(runs) + 1))
+                sub = [runs[int(p)] for p in
+                       sorted(rng.choice(len(runs), size=k, replace=False))]
+            else:
+                picks = {stored[int(j)].key: stored[int(j)] for j in
+                         rng.integers(0, len(stored),
+                                      int(rng.integers(1, 300)))}
+                sub = [build_run([
+                    Entry(key, b"" if rng.random() < 0.2 else e.data[::-1],
+                          e.timestamp if rng.random() < 0.3 else
+                          e.timestamp + int(rng.integers(-3, 4)) *
+                          (1 << int(rng.integers(0, 100)))
+                          if abs(e.timestamp) < (1 << 126) else e.timestamp)
+                    for key, e in sorted(picks.items())])]
+            m = gem.Model(sub)
+            msources.append(m)
+            if rng.random() < 0.5:
+                readers.append(Reader(sub, device=device))
+                sources.append(readers[-1])
+            else:
+                off, rec = mm.answers_of(m, queries)
+                sources.append((np.array(off, dtype=np.uint64),
+                                np.frombuffer(rec, dtype=np.uint8)))
+        MERGED["calls"] += 1
+        MERGED["sources"] += len(sources)
+        ehits, eoff, erec, _, _ = mm.expect(queries, local, msources)
+        cap = int(rng.integers(0, eoff[-1] + 2))
+        _, _, _, erc, epage = mm.expect(queries, local, msources, cap)
+        what = f"get_merged {len(sources)} sources cap {cap}"
+        try:
+            hits, roff, view, page, _ = rd.get_merged_raw(
+                queries, sources, records_cap=cap)
+            rc = 0
+        except DbeelGpuError as e:
+            rc, hits, roff, page = e.code, e.hits, e.record_offsets, e.page
+            view = np.zeros(0, dtype=np.uint8)
+        if rc != erc or page != epage:
+            return f"{what}: rc {rc} page {page}, want {erc} {epage}"
+        want = (np.array(ehits, dtype=MERGE_HIT_DTYPE) if ehits
+                else np.zeros(0, dtype=MERGE_HIT_DTYPE))
+        if not np.array_equal(hits, want):
+            return f"{what}: hits differ from the model"
+        if roff.tolist() != eoff:
+            return f"{what}: record_offsets differ from the model"
+        if view.tobytes() != erec[:epage["records_len"]]:
+            return f"{what}: record bytes differ from the model"
+        page_bytes = int(rng.integers(0, 4096))
+        if (rd.get_merged(queries, sources, page_bytes=page_bytes)
+                != mm.merged(queries, local, msources)):
+            return f"{what}: paging loop at {page_bytes} differs"
+    finally:
+        for r in readers:
+            r.close()
     return None
 
 
@@ -457,7 +537,8 @@ def main():
                 failures += 1
                 print(f"TRIAL {t} SCAN MISMATCH {kw}: n {sn} vs {mn}")
         if args.reader:
-            why = reader_trial(rng, runs, args.device)
+            why = reader_trial(rng, runs, args.device,
+                               np.random.default_rng([args.seed, t, 0x4D]))
             if why:
                 failures += 1
                 print(f"TRIAL {t} READER MISMATCH: {why}")
@@ -466,6 +547,9 @@ def main():
     if failures:
         print(f"FUZZ FAILED: {failures} mismatches")
         sys.exit(1)
+    if args.reader:
+        print(f"get_merged: {MERGED['calls']} batches against the model, "
+              f"{MERGED['sources']} sources in all")
     print(f"FUZZ OK: {args.trials} trials x 2 settings, all bit-identical")
 
 

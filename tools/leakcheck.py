@@ -12,7 +12,8 @@ after a flush / snapshot scans begun, paged and ended across an insert, two
 puts and a compaction, one left for close / close with a non-empty
 memtable / put_entries of a host page, a refused corrupt page, scan_apply
 into a second reader with deletes back into the source, flushes, close with
-that scan open) and compact_into (1 and several slices, pinned and pageable
+that scan open / get_merged with 0, 1 and 3 sources, one of them a reader,
+at two page sizes, and a refused corrupt answer) and compact_into (1 and several slices, pinned and pageable
 destinations, with and without the filter, a refused short cap, a job's
 fetch_into), reporting hipMemGetInfo drift. A leak in any path shows as monotonically shrinking free memory.
 
@@ -243,6 +244,27 @@ def main():
                 dst.memtable_flush(fetch=False)
                 src.memtable_flush(fetch=False)
                 # close ends mig and frees what it holds
+            # replicated reads: get_merged with 0, 1 and 3 sources, one of
+            # them a reader, at two page sizes (candidate, answer and record
+            # scratch are the local reader's and regrow), and one corrupt
+            # answer refused on the device
+            with Reader(runs[:2], device=0) as loc, \
+                    Reader(runs[2:], device=0) as rep, \
+                    Reader(runs2[:2], device=0) as rep2:
+                mk = probe_keys[:20_000]
+                a1 = tuple(x.copy() for x in rep.get_entries_raw(mk)[1:3])
+                a2 = tuple(x.copy() for x in rep2.get_entries_raw(mk)[1:3])
+                for srcs in ([], [a1], [a1, rep2, a2]):
+                    for cap in (64 << 20, 1 << 18):
+                        loc.get_merged(mk, srcs, page_bytes=cap)
+                bad = a1[1].copy()
+                bad[:8] = 0xFF  # the first record's data_len
+                try:
+                    loc.get_merged_raw(mk, [rep2, (a1[0], bad)])
+                    raise SystemExit("get_merged accepted a corrupt answer")
+                except DbeelGpuError as e:
+                    if e.code != 2:
+                        raise
             # compact_into: jobs, events, the hash array and the filter
             # bitmap are the call's; pinned (data) and pageable (index)
             # destinations, 1 and several slices, with and without the
