@@ -2220,6 +2220,9 @@ static uint32_t pick_grid(uint64_t work_items, uint32_t block) {
     return (uint32_t)blocks;
 }
 
+extern "C" uint32_t dbeel_gpu_grid_for(uint64_t work_items, uint32_t block) {
+    return block ? pick_grid(work_items, block) : 0;
+}
 
 /* Copy-geometry selection measured by interleaved A/B (tools/ab_copy.py,
  * r02): ~1 KiB survivors (cfg3) run 11% faster with 64 KiB windows /

@@ -145,8 +145,16 @@ def load() -> ctypes.CDLL:
             ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
             ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(CompactResult),
         ]
+        lib.dbeel_gpu_grid_for.restype = ctypes.c_uint32
+        lib.dbeel_gpu_grid_for.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
         _lib = lib
     return _lib
+
+
+def grid_for(work_items: int, block: int = 256) -> int:
+    """dbeel_gpu_grid_for: the blocks a launch over work_items items gets
+    (capped; a grid-stride loop covers the rest). Host arithmetic only."""
+    return int(load().dbeel_gpu_grid_for(int(work_items), int(block)))
 
 
 def _as_u8(buf) -> np.ndarray:

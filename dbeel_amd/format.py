@@ -148,7 +148,10 @@ def build_run_fixed_key(
     if it.size or not V:
         rows = it if V else np.arange(N)
         M[rows, 16 + K : 24 + K] = ts_bytes[rows]
-    # (timestamp high 8 bytes already zero)
+        # with V < 16 the full-width copy above overlaps a tombstone row's
+        # own timestamp field: its high half must be zero again
+        M[rows, 24 + K : 32 + K] = 0
+    # (timestamp high 8 bytes zero everywhere)
 
     if uniform:
         data = flat

@@ -1023,6 +1023,14 @@ typedef struct {
 
 int dbeel_gpu_pin_host(const void* ptr, size_t len);
 int dbeel_gpu_unpin_host(const void* ptr);
+
+/* The grid every launch outside the copy and co-rank kernels uses for
+ * work_items items (or work_items * 64 lanes for a wave-per-item kernel) in
+ * blocks of `block` threads: ceil(work_items / block), at least 1, capped;
+ * past the cap the kernels cover the rest with a grid-stride loop. Pure host
+ * arithmetic, no device call; block == 0 returns 0. Exported so that tests
+ * can size their inputs past the cap whatever its value. */
+uint32_t dbeel_gpu_grid_for(uint64_t work_items, uint32_t block);
 int dbeel_gpu_job_ingest(dbeel_gpu_job* job, const dbeel_run_view* runs,
                          size_t n_runs, dbeel_ingest_stats* stats);
 

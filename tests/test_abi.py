@@ -27,6 +27,7 @@ HEADER_SYMBOLS = [
     "dbeel_gpu_scan",
     "dbeel_gpu_pin_host",
     "dbeel_gpu_unpin_host",
+    "dbeel_gpu_grid_for",
 ]
 
 LSM_SYMBOLS = [
