@@ -94,6 +94,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "../../include/dbeel_gpu.h"
+#include "engine_internal.h"
 
 #define MAX_RUNS 64
 
@@ -110,8 +111,7 @@ extern "C" const char* dbeel_gpu_last_error(void) { return g_err; }
 
 /* Library-internal: lets the file-level layer (dbeel_lsm.cpp, linked into
  * the same .so) report through dbeel_gpu_last_error. Not exported. */
-extern "C" __attribute__((visibility("hidden"))) void dbeel_set_last_error(
-    const char* msg) {
+extern "C" void dbeel_set_last_error(const char* msg) {
     set_err("%s", msg);
 }
 
@@ -167,6 +167,15 @@ static int select_device(int device) {
     }
     HIP_CHECK(hipSetDevice(device));
     return DBEEL_OK;
+}
+
+/* The launch grid of every grid-stride kernel. */
+static uint32_t pick_grid(uint64_t work_items, uint32_t block) {
+    uint64_t blocks = (work_items + block - 1) / block;
+    /* 256 CUs x 8 workgroups/CU = 2048; cap and grid-stride the rest */
+    if (blocks > 2048) blocks = 2048;
+    if (blocks == 0) blocks = 1;
+    return (uint32_t)blocks;
 }
 
 /* ------------------------------------------------------------------ */
@@ -1348,8 +1357,6 @@ __global__ __launch_bounds__(BLK) void k_copy(
 /* written by lane 0.                                                 */
 /* ------------------------------------------------------------------ */
 
-static uint32_t pick_grid(uint64_t work_items, uint32_t block);
-
 __global__ void k_encode_sizes(uint64_t n, const uint64_t* key_off,
                                const uint64_t* val_off, uint64_t* sizes) {
     uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
@@ -2210,14 +2217,6 @@ extern "C" int dbeel_gpu_job_ingest(dbeel_gpu_job* job,
     job->h2d_ms = 0.0; /* transfer accounted in ingest stats */
     job->prep_valid = 1;
     return DBEEL_OK;
-}
-
-static uint32_t pick_grid(uint64_t work_items, uint32_t block) {
-    uint64_t blocks = (work_items + block - 1) / block;
-    /* 256 CUs x 8 workgroups/CU = 2048; cap and grid-stride the rest */
-    if (blocks > 2048) blocks = 2048;
-    if (blocks == 0) blocks = 1;
-    return (uint32_t)blocks;
 }
 
 extern "C" uint32_t dbeel_gpu_grid_for(uint64_t work_items, uint32_t block) {
@@ -3275,6 +3274,26 @@ static hipError_t reader_link(dbeel_gpu_reader* rd) {
     return e;
 }
 
+/* The list edit of every new table (insert_run, write_batch,
+ * memtable_flush): t goes in at pos and the descriptor is linked again. On a
+ * failed link the edit is undone, the old list linked back and t is still
+ * the caller's to free. Once linked, open scans are stale (the generation
+ * moves) and a pending compaction keeps naming the same tables. */
+static hipError_t reader_insert_table(dbeel_gpu_reader* rd, size_t pos,
+                                      const ReaderTable& t) {
+    rd->tables.insert(rd->tables.begin() + pos, t);
+    hipError_t e = reader_link(rd);
+    if (e != hipSuccess) {
+        rd->tables.erase(rd->tables.begin() + pos);
+        (void)reader_link(rd);
+        return e;
+    }
+    rd->generation++;
+    for (uint32_t& p : rd->pending_pos)
+        if (p >= pos) p++;
+    return hipSuccess;
+}
+
 extern "C" void dbeel_gpu_reader_compact_abort(dbeel_gpu_reader* rd) {
     if (!rd || !rd->has_pending) return;
     if (rd->device >= 0) (void)hipSetDevice(rd->device);
@@ -3325,8 +3344,7 @@ extern "C" size_t dbeel_gpu_reader_run_count(const dbeel_gpu_reader* rd) {
 }
 
 /* Library-internal (dbeel_lsm.cpp's bloom gate): data bytes of run pos. */
-extern "C" __attribute__((visibility("hidden"))) uint64_t
-dbeel_reader_run_data_len(const dbeel_gpu_reader* rd, size_t pos) {
+extern "C" uint64_t dbeel_reader_run_data_len(const dbeel_gpu_reader* rd, size_t pos) {
     return (rd && pos < rd->tables.size()) ? rd->tables[pos].data_len : 0;
 }
 
@@ -3523,12 +3541,9 @@ extern "C" int dbeel_gpu_reader_insert_run(dbeel_gpu_reader* rd, size_t pos,
         table_free(t);
         return DBEEL_ERR_CORRUPT;
     }
-    rd->tables.insert(rd->tables.begin() + pos, t);
-    rd->generation++; /* open scans are stale from here on */
-    /* a pending compaction keeps naming the same tables */
-    for (uint32_t& p : rd->pending_pos)
-        if (p >= pos) p++;
-    HIP_CHECK(reader_link(rd));
+    e = reader_insert_table(rd, pos, t);
+    if (e != hipSuccess) table_free(t);
+    HIP_CHECK(e);
     return DBEEL_OK;
 }
 
@@ -4102,9 +4117,6 @@ static int batch_merge_sort(BatchStage& b, uint64_t m, hipStream_t s) {
     return DBEEL_OK;
 }
 
-static int batch_sort_flag(BatchStage& b, int tomb, uint64_t bound,
-                           hipStream_t s, hipEvent_t* ev);
-
 /* The slab and the rocPRIM scratch for n writes: the arrays' staging
  * (kbytes of keys, vbytes of values; a page has no arrays and stages
  * nothing of them) plus `extra` bytes for the caller, at b.extra. */
@@ -4164,41 +4176,6 @@ static int batch_alloc(BatchStage& b, uint32_t n, bool arrays,
     HIP_CHECK(hipMalloc(&b.d_tmp, tmp_bytes ? tmp_bytes : 1));
     b.tmp_bytes = tmp_bytes;
     return DBEEL_OK;
-}
-
-/* Steps 1-4 on stream s: upload, prefixes, order, survivor flags and
- * scans; returns with the stream idle and n_surv / total_bytes /
- * prefix_tied known to the host. ev (NULL or 3 events) receives the marks
- * start | uploaded | ordered. The input was validated: in.n in [1, 2^31). */
-static int batch_order(BatchStage& b, const BatchIn& in, hipStream_t s,
-                       hipEvent_t* ev) {
-    const uint32_t n = b.n = (uint32_t)in.n;
-    const uint64_t kbytes = in.koff[n], vbytes = in.voff[n];
-    int rc = batch_alloc(b, n, true, kbytes, vbytes, 0, s);
-    if (rc) return rc;
-
-    /* 1. upload */
-    if (ev) HIP_CHECK(hipEventRecord(ev[0], s));
-    if (kbytes)
-        HIP_CHECK(hipMemcpyAsync(b.keys, in.keys, kbytes,
-                                 hipMemcpyHostToDevice, s));
-    if (vbytes)
-        HIP_CHECK(hipMemcpyAsync(b.vals, in.vals, vbytes,
-                                 hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(b.ts, in.ts, (uint64_t)n * 16,
-                             hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(b.koff, in.koff, (uint64_t)(n + 1) * 8,
-                             hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(b.voff, in.voff, (uint64_t)(n + 1) * 8,
-                             hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemsetAsync(b.zero, 0, 16, s));
-    if (ev) HIP_CHECK(hipEventRecord(ev[1], s));
-
-    /* 2. prefixes */
-    b.K = {b.keys, b.koff, n, nullptr};
-    hipLaunchKernelGGL(k_batch_prefix, dim3(pick_grid(n, 256)), dim3(256), 0,
-                       s, b.K, b.pfx[0], b.arr[0]);
-    return batch_sort_flag(b, 0, 32ull * n + kbytes + vbytes, s, ev);
 }
 
 /* Steps 3-4 over the b.n writes whose prefixes and arrival indices lie in
@@ -4293,6 +4270,41 @@ static int batch_sort_flag(BatchStage& b, int tomb, uint64_t bound,
         return DBEEL_ERR_HIP;
     }
     return DBEEL_OK;
+}
+
+/* Steps 1-4 on stream s: upload, prefixes, order, survivor flags and
+ * scans; returns with the stream idle and n_surv / total_bytes /
+ * prefix_tied known to the host. ev (NULL or 3 events) receives the marks
+ * start | uploaded | ordered. The input was validated: in.n in [1, 2^31). */
+static int batch_order(BatchStage& b, const BatchIn& in, hipStream_t s,
+                       hipEvent_t* ev) {
+    const uint32_t n = b.n = (uint32_t)in.n;
+    const uint64_t kbytes = in.koff[n], vbytes = in.voff[n];
+    int rc = batch_alloc(b, n, true, kbytes, vbytes, 0, s);
+    if (rc) return rc;
+
+    /* 1. upload */
+    if (ev) HIP_CHECK(hipEventRecord(ev[0], s));
+    if (kbytes)
+        HIP_CHECK(hipMemcpyAsync(b.keys, in.keys, kbytes,
+                                 hipMemcpyHostToDevice, s));
+    if (vbytes)
+        HIP_CHECK(hipMemcpyAsync(b.vals, in.vals, vbytes,
+                                 hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(b.ts, in.ts, (uint64_t)n * 16,
+                             hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(b.koff, in.koff, (uint64_t)(n + 1) * 8,
+                             hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(b.voff, in.voff, (uint64_t)(n + 1) * 8,
+                             hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemsetAsync(b.zero, 0, 16, s));
+    if (ev) HIP_CHECK(hipEventRecord(ev[1], s));
+
+    /* 2. prefixes */
+    b.K = {b.keys, b.koff, n, nullptr};
+    hipLaunchKernelGGL(k_batch_prefix, dim3(pick_grid(n, 256)), dim3(256), 0,
+                       s, b.K, b.pfx[0], b.arr[0]);
+    return batch_sort_flag(b, 0, 32ull * n + kbytes + vbytes, s, ev);
 }
 
 /* ---- A page of run-format entries as the batch (put_entries) ---- */
@@ -4580,28 +4592,17 @@ extern "C" int dbeel_gpu_reader_write_batch(
     st.prefix_tied = b.prefix_tied;
     st.d2h_bytes = d2h_bytes;
 
-    /* the list edit of insert_run; on a failed link the edit is undone */
-    rd->tables.insert(rd->tables.begin() + pos, t);
-    hipError_t e = reader_link(rd);
-    if (e != hipSuccess) {
-        rd->tables.erase(rd->tables.begin() + pos);
-        (void)reader_link(rd);
-        HIP_CHECK(e);
-    }
+    hipError_t e = reader_insert_table(rd, pos, t);
+    HIP_CHECK(e); /* the guard above frees t */
     linked = true;
-    rd->generation++; /* open scans are stale from here on */
-    /* a pending compaction keeps naming the same tables */
-    for (uint32_t& p : rd->pending_pos)
-        if (p >= pos) p++;
     if (stats) *stats = st;
     return DBEEL_OK;
 }
 
 /* Library-internal (dbeel_lsm.cpp: a flush whose files could not be
  * written): takes the table at pos out of the list again — the inverse of
- * the list edit above. */
-extern "C" __attribute__((visibility("hidden"))) int dbeel_reader_drop_run(
-    dbeel_gpu_reader* rd, size_t pos) {
+ * reader_insert_table. */
+extern "C" int dbeel_reader_drop_run(dbeel_gpu_reader* rd, size_t pos) {
     if (!rd || pos >= rd->tables.size()) return DBEEL_ERR_INVALID_ARG;
     HIP_CHECK(hipSetDevice(rd->device));
     HIP_CHECK(hipStreamSynchronize(rd->stream));
@@ -5260,16 +5261,9 @@ extern "C" int dbeel_gpu_reader_memtable_flush(dbeel_gpu_reader* rd,
         int rc = table_bloom_fetch(t, s, bloom_bytes, bloom_len);
         if (rc) return rc;
     }
-    /* the list edit of a push; on a failed link the edit is undone */
-    rd->tables.push_back(t);
-    hipError_t e = reader_link(rd);
-    if (e != hipSuccess) {
-        rd->tables.pop_back();
-        (void)reader_link(rd);
-        HIP_CHECK(e);
-    }
+    hipError_t e = reader_insert_table(rd, rd->tables.size(), t);
+    HIP_CHECK(e); /* the guard above frees t */
     linked = true;
-    rd->generation++; /* open scans are stale from here on */
     M.drop();
     return DBEEL_OK;
 }
@@ -5280,6 +5274,94 @@ extern "C" void dbeel_gpu_get_result_free(dbeel_get_result* r) {
     free(r->value_offsets);
     free(r->values);
     memset(r, 0, sizeof *r);
+}
+
+/* ---- The key batch of the read family (get, get_entries, get_merged):
+ * one definition of what all three do before their paths part. ---- */
+
+/* The two refusals of a key batch, under the caller's name. */
+static int keys_check(const char* who, const uint64_t* key_offsets,
+                      uint64_t n_keys) {
+    if (n_keys >= (1ull << 32)) {
+        set_err("%s: 2^32 or more keys in one batch", who);
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    for (uint64_t i = 0; i < n_keys; i++)
+        if (key_offsets[i + 1] < key_offsets[i]) {
+            set_err("%s: key_offsets not ascending at %llu", who,
+                    (unsigned long long)i);
+            return DBEEL_ERR_INVALID_ARG;
+        }
+    return DBEEL_OK;
+}
+
+/* d_batch layout: key offsets (n+1) | result offsets (n+1) | hits (n+1, the
+ * last one a sentinel whose length is zero, so the scan's final element is
+ * the total; which bytes say "zero length" is the caller's functor's
+ * business, and so is writing them). */
+struct KeyBatch {
+    uint64_t* koff;
+    uint64_t* roff;
+    dbeel_lookup_hit* hits;
+};
+
+/* Reserves d_keys and d_batch for n keys and lays the batch out. */
+static int keys_reserve(dbeel_gpu_reader* rd, const uint64_t* key_offsets,
+                        uint64_t n, KeyBatch& kb) {
+    const uint64_t kbytes = key_offsets[n];
+    HIP_CHECK(reader_reserve((void**)&rd->d_keys, &rd->keys_cap,
+                             kbytes ? kbytes : 1));
+    HIP_CHECK(reader_reserve((void**)&rd->d_batch, &rd->batch_cap,
+                             2 * (n + 1) * sizeof(uint64_t) +
+                                 (n + 1) * sizeof(dbeel_lookup_hit)));
+    kb.koff = (uint64_t*)rd->d_batch;
+    kb.roff = kb.koff + (n + 1);
+    kb.hits = (dbeel_lookup_hit*)(kb.roff + (n + 1));
+    return DBEEL_OK;
+}
+
+/* Keys and offsets to the device, the search counters cleared. */
+static int keys_upload(dbeel_gpu_reader* rd, const uint8_t* keys,
+                       const uint64_t* key_offsets, uint64_t n,
+                       const KeyBatch& kb) {
+    hipStream_t s = rd->stream;
+    const uint64_t kbytes = key_offsets[n];
+    if (kbytes)
+        HIP_CHECK(hipMemcpyAsync(rd->d_keys, keys, kbytes,
+                                 hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(kb.koff, key_offsets,
+                             (n + 1) * sizeof(uint64_t),
+                             hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemsetAsync(rd->d_stats, 0, RS_N * sizeof(uint64_t), s));
+    return DBEEL_OK;
+}
+
+/* Searches rd's tables (and its memtable, when it holds anything) for the n
+ * keys on stream s: one hit record per key into `hits`, counters into rd's
+ * d_stats. The keys may be another reader's upload (get_merged's sources). */
+static void reader_search(const dbeel_gpu_reader* rd, hipStream_t s,
+                          const uint8_t* d_keys, const uint64_t* d_koff,
+                          uint64_t n, dbeel_lookup_hit* hits) {
+    typedef void (*SearchFn)(RunsDesc, ReaderPfx, ReaderMem,
+                             const ReaderBloom*, const uint8_t*,
+                             const uint64_t*, uint64_t, dbeel_lookup_hit*,
+                             unsigned long long*);
+    SearchFn ks = k_reader_search<false>;
+    if (rd->mem.count) ks = k_reader_search<true>;
+    hipLaunchKernelGGL(ks, dim3(pick_grid(n, READER_BLOCK)),
+                       dim3(READER_BLOCK), 0, s, rd->desc, rd->pfx,
+                       rd->mem.view(), rd->d_blooms, d_keys, d_koff, n, hits,
+                       rd->d_stats);
+}
+
+/* The search counters as get and get_entries report them. */
+static void stats_counters(dbeel_get_stats* stats,
+                           const unsigned long long* hstats) {
+    stats->bloom_probes = hstats[RS_PROBES];
+    stats->bloom_skips = hstats[RS_SKIPS];
+    stats->searches = hstats[RS_SEARCHES];
+    stats->hits = hstats[RS_HITS];
+    stats->tombstones = hstats[RS_TOMBS];
 }
 
 extern "C" int dbeel_gpu_reader_get(dbeel_gpu_reader* rd,
@@ -5294,16 +5376,7 @@ extern "C" int dbeel_gpu_reader_get(dbeel_gpu_reader* rd,
         return DBEEL_ERR_INVALID_ARG;
     }
     memset(out, 0, sizeof *out);
-    if (n_keys >= (1ull << 32)) {
-        set_err("reader_get: 2^32 or more keys in one batch");
-        return DBEEL_ERR_INVALID_ARG;
-    }
-    for (uint64_t i = 0; i < n_keys; i++)
-        if (key_offsets[i + 1] < key_offsets[i]) {
-            set_err("reader_get: key_offsets not ascending at %llu",
-                    (unsigned long long)i);
-            return DBEEL_ERR_INVALID_ARG;
-        }
+    if (int rc = keys_check("reader_get", key_offsets, n_keys)) return rc;
     const uint64_t n = n_keys;
     out->hits = (dbeel_lookup_hit*)malloc((n ? n : 1) * sizeof *out->hits);
     out->value_offsets = (uint64_t*)calloc(n + 1, sizeof(uint64_t));
@@ -5317,9 +5390,6 @@ extern "C" int dbeel_gpu_reader_get(dbeel_gpu_reader* rd,
         return DBEEL_OK;
     }
 
-    const uint64_t kbytes = key_offsets[n];
-    /* d_batch layout: key offsets (n+1) | value offsets (n+1) | hits (n+1,
-     * the last one zeroed so the scan's final element is the total) */
     const uint64_t off_bytes = (n + 1) * sizeof(uint64_t);
     size_t tmp_bytes = 0;
     uint64_t total = 0;
@@ -5334,14 +5404,10 @@ extern "C" int dbeel_gpu_reader_get(dbeel_gpu_reader* rd,
     });
 
     HIP_CHECK(hipSetDevice(rd->device));
-    HIP_CHECK(reader_reserve((void**)&rd->d_keys, &rd->keys_cap,
-                             kbytes ? kbytes : 1));
-    HIP_CHECK(reader_reserve((void**)&rd->d_batch, &rd->batch_cap,
-                             2 * off_bytes +
-                                 (n + 1) * sizeof(dbeel_lookup_hit)));
-    uint64_t* d_koff = (uint64_t*)rd->d_batch;
-    uint64_t* d_voff = d_koff + (n + 1);
-    dbeel_lookup_hit* d_hits = (dbeel_lookup_hit*)(d_voff + (n + 1));
+    KeyBatch kb;
+    if (int rc = keys_reserve(rd, key_offsets, n, kb)) return rc;
+    uint64_t* d_voff = kb.roff;
+    dbeel_lookup_hit* d_hits = kb.hits;
     HIP_CHECK(rocprim::exclusive_scan(
         nullptr, tmp_bytes,
         rocprim::make_transform_iterator(d_hits, HitValueLen{}), d_voff,
@@ -5350,22 +5416,11 @@ extern "C" int dbeel_gpu_reader_get(dbeel_gpu_reader* rd,
                              tmp_bytes ? tmp_bytes : 1));
 
     HIP_CHECK(hipEventRecord(rd->ev[0], s));
-    if (kbytes)
-        HIP_CHECK(hipMemcpyAsync(rd->d_keys, keys, kbytes,
-                                 hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(d_koff, key_offsets, off_bytes,
-                             hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemsetAsync(rd->d_stats, 0, RS_N * sizeof(uint64_t), s));
+    if (int rc = keys_upload(rd, keys, key_offsets, n, kb)) return rc;
+    /* the sentinel: zeroed, value_len 0 */
     HIP_CHECK(hipMemsetAsync(d_hits + n, 0, sizeof(dbeel_lookup_hit), s));
     HIP_CHECK(hipEventRecord(rd->ev[1], s));
-    void (*ks)(RunsDesc, ReaderPfx, ReaderMem, const ReaderBloom*,
-               const uint8_t*, const uint64_t*, uint64_t, dbeel_lookup_hit*,
-               unsigned long long*) = k_reader_search<false>;
-    if (rd->mem.count) ks = k_reader_search<true>;
-    hipLaunchKernelGGL(ks, dim3(pick_grid(n, READER_BLOCK)),
-                       dim3(READER_BLOCK),
-                       0, s, rd->desc, rd->pfx, rd->mem.view(), rd->d_blooms,
-                       rd->d_keys, d_koff, n, d_hits, rd->d_stats);
+    reader_search(rd, s, rd->d_keys, kb.koff, n, d_hits);
     HIP_CHECK(hipEventRecord(rd->ev[2], s));
     HIP_CHECK(rocprim::exclusive_scan(
         rd->d_scantmp, tmp_bytes,
@@ -5415,11 +5470,7 @@ extern "C" int dbeel_gpu_reader_get(dbeel_gpu_reader* rd,
                                              sizing the output) is not
                                              device work */
         stats->d2h_ms = ms[5];
-        stats->bloom_probes = hstats[RS_PROBES];
-        stats->bloom_skips = hstats[RS_SKIPS];
-        stats->searches = hstats[RS_SEARCHES];
-        stats->hits = hstats[RS_HITS];
-        stats->tombstones = hstats[RS_TOMBS];
+        stats_counters(stats, hstats);
     }
     fail.dismiss();
     return DBEEL_OK;
@@ -5488,25 +5539,14 @@ extern "C" int dbeel_gpu_reader_get_entries(
                 (unsigned long long)buf->records_cap);
         return DBEEL_ERR_INVALID_ARG;
     }
-    if (n_keys >= (1ull << 32)) {
-        set_err("reader_get_entries: 2^32 or more keys in one batch");
-        return DBEEL_ERR_INVALID_ARG;
-    }
-    for (uint64_t i = 0; i < n_keys; i++)
-        if (key_offsets[i + 1] < key_offsets[i]) {
-            set_err("reader_get_entries: key_offsets not ascending at %llu",
-                    (unsigned long long)i);
-            return DBEEL_ERR_INVALID_ARG;
-        }
+    if (int rc = keys_check("reader_get_entries", key_offsets, n_keys))
+        return rc;
     const uint64_t n = n_keys;
     if (n == 0) {
         if (buf->record_offsets) buf->record_offsets[0] = 0;
         return DBEEL_OK;
     }
 
-    const uint64_t kbytes = key_offsets[n];
-    /* d_batch layout: key offsets (n+1) | record offsets (n+1) | hits (n+1,
-     * the last one absent so the scan's final element is the total) */
     const uint64_t off_bytes = (n + 1) * sizeof(uint64_t);
     size_t tmp_bytes = 0;
     unsigned long long hstats[RS_N] = {};
@@ -5517,14 +5557,10 @@ extern "C" int dbeel_gpu_reader_get_entries(
     ScopeGuard fail([&] { (void)hipStreamSynchronize(s); });
 
     HIP_CHECK(hipSetDevice(rd->device));
-    HIP_CHECK(reader_reserve((void**)&rd->d_keys, &rd->keys_cap,
-                             kbytes ? kbytes : 1));
-    HIP_CHECK(reader_reserve((void**)&rd->d_batch, &rd->batch_cap,
-                             2 * off_bytes +
-                                 (n + 1) * sizeof(dbeel_lookup_hit)));
-    uint64_t* d_koff = (uint64_t*)rd->d_batch;
-    uint64_t* d_roff = d_koff + (n + 1);
-    dbeel_lookup_hit* d_hits = (dbeel_lookup_hit*)(d_roff + (n + 1));
+    KeyBatch kb;
+    if (int rc = keys_reserve(rd, key_offsets, n, kb)) return rc;
+    uint64_t* d_roff = kb.roff;
+    dbeel_lookup_hit* d_hits = kb.hits;
     HIP_CHECK(rocprim::exclusive_scan(
         nullptr, tmp_bytes,
         rocprim::make_transform_iterator(d_hits, HitRecordLen{}), d_roff,
@@ -5533,23 +5569,11 @@ extern "C" int dbeel_gpu_reader_get_entries(
                              tmp_bytes ? tmp_bytes : 1));
 
     HIP_CHECK(hipEventRecord(rd->ev[0], s));
-    if (kbytes)
-        HIP_CHECK(hipMemcpyAsync(rd->d_keys, keys, kbytes,
-                                 hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(d_koff, key_offsets, off_bytes,
-                             hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemsetAsync(rd->d_stats, 0, RS_N * sizeof(uint64_t), s));
-    /* all-ones bytes: run = -1 */
+    if (int rc = keys_upload(rd, keys, key_offsets, n, kb)) return rc;
+    /* the sentinel: all-ones bytes, run = -1 */
     HIP_CHECK(hipMemsetAsync(d_hits + n, 0xFF, sizeof(dbeel_lookup_hit), s));
     HIP_CHECK(hipEventRecord(rd->ev[1], s));
-    void (*ks)(RunsDesc, ReaderPfx, ReaderMem, const ReaderBloom*,
-               const uint8_t*, const uint64_t*, uint64_t, dbeel_lookup_hit*,
-               unsigned long long*) = k_reader_search<false>;
-    if (rd->mem.count) ks = k_reader_search<true>;
-    hipLaunchKernelGGL(ks, dim3(pick_grid(n, READER_BLOCK)),
-                       dim3(READER_BLOCK),
-                       0, s, rd->desc, rd->pfx, rd->mem.view(), rd->d_blooms,
-                       rd->d_keys, d_koff, n, d_hits, rd->d_stats);
+    reader_search(rd, s, rd->d_keys, kb.koff, n, d_hits);
     HIP_CHECK(hipEventRecord(rd->ev[2], s));
     HIP_CHECK(rocprim::exclusive_scan(
         rd->d_scantmp, tmp_bytes,
@@ -5610,11 +5634,7 @@ extern "C" int dbeel_gpu_reader_get_entries(
         stats->search_ms = ms[1];
         stats->gather_ms = ms[2] + ms[4]; /* offset scan + record gather */
         stats->d2h_ms = ms[3] + ms[5];    /* every copy to the caller    */
-        stats->bloom_probes = hstats[RS_PROBES];
-        stats->bloom_skips = hstats[RS_SKIPS];
-        stats->searches = hstats[RS_SEARCHES];
-        stats->hits = hstats[RS_HITS];
-        stats->tombstones = hstats[RS_TOMBS];
+        stats_counters(stats, hstats);
     }
     fail.dismiss();
     if (n_done == 0) { /* n > 0: record 0 alone is over the cap */
@@ -5834,16 +5854,7 @@ extern "C" int dbeel_gpu_reader_get_merged(
                 (unsigned long long)buf->records_cap);
         return DBEEL_ERR_INVALID_ARG;
     }
-    if (n_keys >= (1ull << 32)) {
-        set_err("%s: 2^32 or more keys in one batch", who);
-        return DBEEL_ERR_INVALID_ARG;
-    }
-    for (uint64_t i = 0; i < n_keys; i++)
-        if (key_offsets[i + 1] < key_offsets[i]) {
-            set_err("%s: key_offsets not ascending at %llu", who,
-                    (unsigned long long)i);
-            return DBEEL_ERR_INVALID_ARG;
-        }
+    if (int rc = keys_check(who, key_offsets, n_keys)) return rc;
     if (n_sources > DBEEL_MERGE_MAX_SOURCES) {
         set_err("%s: %zu sources, at most %d", who, n_sources,
                 DBEEL_MERGE_MAX_SOURCES);
@@ -5912,7 +5923,6 @@ extern "C" int dbeel_gpu_reader_get_merged(
     }
 
     const uint32_t n_cand = (uint32_t)n_sources + 1;
-    const uint64_t kbytes = key_offsets[n];
     const uint64_t off_bytes = (n + 1) * sizeof(uint64_t);
     /* the uploaded answers, each as offsets | records, 8-B aligned */
     uint64_t ans_bytes = 0;
@@ -5941,12 +5951,12 @@ extern "C" int dbeel_gpu_reader_get_merged(
     });
 
     HIP_CHECK(hipSetDevice(rd->device));
-    HIP_CHECK(reader_reserve((void**)&rd->d_keys, &rd->keys_cap,
-                             kbytes ? kbytes : 1));
-    /* d_batch as get_entries lays it out; its record-offset slot is unused */
-    HIP_CHECK(reader_reserve((void**)&rd->d_batch, &rd->batch_cap,
-                             2 * off_bytes +
-                                 (n + 1) * sizeof(dbeel_lookup_hit)));
+    /* the key batch's result-offset slot and sentinel hit are unused here:
+     * the offsets scanned are the winners', in d_merge. kb's pointers stay
+     * good through the sources' reservations below only because no source
+     * is rd itself (refused above): those grow other readers' d_batch. */
+    KeyBatch kb;
+    if (int rc = keys_reserve(rd, key_offsets, n, kb)) return rc;
     HIP_CHECK(reader_reserve((void**)&rd->d_merge, &rd->merge_cap,
                              merge_bytes));
     HIP_CHECK(reader_reserve((void**)&rd->d_answers, &rd->answers_cap,
@@ -5957,8 +5967,6 @@ extern "C" int dbeel_gpu_reader_get_merged(
             HIP_CHECK(reader_reserve((void**)&sr->d_batch, &sr->batch_cap,
                                      n * sizeof(dbeel_lookup_hit)));
         }
-    uint64_t* d_koff = (uint64_t*)rd->d_batch;
-    dbeel_lookup_hit* d_hits = (dbeel_lookup_hit*)(d_koff + 2 * (n + 1));
     MergeCand* d_cand = (MergeCand*)rd->d_merge;
     MergeCand* d_win = d_cand + (uint64_t)n_cand * n;
     uint64_t* d_roff = (uint64_t*)(d_win + (n + 1));
@@ -5972,11 +5980,7 @@ extern "C" int dbeel_gpu_reader_get_merged(
                              tmp_bytes ? tmp_bytes : 1));
 
     HIP_CHECK(hipEventRecord(rd->ev[0], s));
-    if (kbytes)
-        HIP_CHECK(hipMemcpyAsync(rd->d_keys, keys, kbytes,
-                                 hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(d_koff, key_offsets, off_bytes,
-                             hipMemcpyHostToDevice, s));
+    if (int rc = keys_upload(rd, keys, key_offsets, n, kb)) return rc;
     uint64_t ans_at = 0;
     for (size_t i = 0; i < n_sources; i++) {
         if (sources[i].kind != DBEEL_MERGE_ANSWERS) continue;
@@ -5990,7 +5994,6 @@ extern "C" int dbeel_gpu_reader_get_merged(
                                      hipMemcpyHostToDevice, s));
         ans_at += off_bytes + round8(rb);
     }
-    HIP_CHECK(hipMemsetAsync(rd->d_stats, 0, RS_N * sizeof(uint64_t), s));
     HIP_CHECK(hipMemsetAsync(d_tot, 0, sizeof *d_tot, s));
     HIP_CHECK(hipMemsetAsync(&d_tot->err, 0xFF, sizeof d_tot->err, s));
     HIP_CHECK(hipMemsetAsync(d_win + n, 0, sizeof(MergeCand), s));
@@ -5998,10 +6001,6 @@ extern "C" int dbeel_gpu_reader_get_merged(
 
     /* every reader candidate is searched as get_entries searches it; a
      * source on its own stream, once the keys are up, into its own scratch */
-    typedef void (*SearchFn)(RunsDesc, ReaderPfx, ReaderMem,
-                             const ReaderBloom*, const uint8_t*,
-                             const uint64_t*, uint64_t, dbeel_lookup_hit*,
-                             unsigned long long*);
     for (size_t i = 0; i < n_sources; i++) {
         if (sources[i].kind != DBEEL_MERGE_READER) continue;
         dbeel_gpu_reader* sr = sources[i].reader;
@@ -6009,23 +6008,11 @@ extern "C" int dbeel_gpu_reader_get_merged(
         HIP_CHECK(hipMemsetAsync(sr->d_stats, 0, RS_N * sizeof(uint64_t),
                                  sr->stream));
         HIP_CHECK(hipEventRecord(sr->ev[0], sr->stream));
-        SearchFn ks = k_reader_search<false>;
-        if (sr->mem.count) ks = k_reader_search<true>;
-        hipLaunchKernelGGL(ks, dim3(pick_grid(n, READER_BLOCK)),
-                           dim3(READER_BLOCK), 0, sr->stream, sr->desc,
-                           sr->pfx, sr->mem.view(), sr->d_blooms, rd->d_keys,
-                           d_koff, n, (dbeel_lookup_hit*)sr->d_batch,
-                           sr->d_stats);
+        reader_search(sr, sr->stream, rd->d_keys, kb.koff, n,
+                      (dbeel_lookup_hit*)sr->d_batch);
         HIP_CHECK(hipEventRecord(sr->ev[1], sr->stream));
     }
-    {
-        SearchFn ks = k_reader_search<false>;
-        if (rd->mem.count) ks = k_reader_search<true>;
-        hipLaunchKernelGGL(ks, dim3(pick_grid(n, READER_BLOCK)),
-                           dim3(READER_BLOCK), 0, s, rd->desc, rd->pfx,
-                           rd->mem.view(), rd->d_blooms, rd->d_keys, d_koff,
-                           n, d_hits, rd->d_stats);
-    }
+    reader_search(rd, s, rd->d_keys, kb.koff, n, kb.hits);
     HIP_CHECK(hipEventRecord(rd->ev[2], s));
     /* a source's hit records are read on the local stream: its own stream
      * is drained first */
@@ -6046,7 +6033,7 @@ extern "C" int dbeel_gpu_reader_get_merged(
         MergeCand* out = d_cand + (uint64_t)c * n;
         if (c == n_sources) {
             hipLaunchKernelGGL(k_merge_stage, grid_n, block, 0, s, rd->desc,
-                               rd->mem.view().data, d_hits, nullptr, nullptr,
+                               rd->mem.view().data, kb.hits, nullptr, nullptr,
                                n, c, out, &d_tot->err);
         } else if (sources[c].kind == DBEEL_MERGE_READER) {
             const dbeel_gpu_reader* sr = sources[c].reader;
@@ -7481,44 +7468,35 @@ static inline const uint8_t* host_entry_key(const dbeel_run_view* run,
     return run->data + off + 8;
 }
 
-extern "C" int dbeel_gpu_compact_sliced(const dbeel_run_view* runs,
-                                        size_t n_runs, int keep_tombstones,
-                                        int device,
-                                        uint64_t max_resident_bytes,
-                                        dbeel_compact_result* out) {
-    g_err[0] = 0;
-    if (!out) {
-        set_err("out is null");
-        return DBEEL_ERR_INVALID_ARG;
-    }
-    int rc = validate_runs(runs, n_runs);
-    if (rc) return rc;
-    rc = check_device_arg(device);
-    if (rc) return rc;
-    uint64_t total_input = 0, max_count = 0;
-    size_t big_run = 0;
+/* Bytes of a compaction's input (what the slice count is sized from), with
+ * the run that has the most entries (where the pivots come from) and its
+ * entry count. */
+static uint64_t input_extent(const dbeel_run_view* runs, size_t n_runs,
+                             size_t* big_run, uint64_t* max_count) {
+    uint64_t total_input = 0;
+    *big_run = 0;
+    *max_count = 0;
     for (size_t r = 0; r < n_runs; r++) {
         total_input += runs[r].data_len + runs[r].index_len;
         uint64_t c = runs[r].index_len / 16;
-        if (c > max_count) {
-            max_count = c;
-            big_run = r;
+        if (c > *max_count) {
+            *max_count = c;
+            *big_run = r;
         }
     }
-    uint64_t budget = max_resident_bytes;
-    if (!budget) {
-        HIP_CHECK(hipSetDevice(device));
-        size_t free_b = 0, total_b = 0;
-        HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-        /* input slab + output data + pfx/aux/cr/rrec intermediates stay
-         * under ~2.6x input for <= 64 runs; /3 leaves headroom */
-        budget = (uint64_t)(free_b / 3);
-    }
-    uint64_t S = budget ? (total_input + budget - 1) / budget : 1;
-    if (S <= 1 || max_count < 2 * S)
-        return dbeel_gpu_compact(runs, n_runs, keep_tombstones, device, out);
+    return total_input;
+}
 
-    /* pivots: evenly spaced keys of the largest run */
+/* The host slicer: S slices of every run. Pivots are evenly spaced keys of
+ * the largest run, bounds[r][sl] the first entry of run r not below pivot sl
+ * (S + 1 values, from 0 to the run's count, appended to the n_runs empty
+ * lists the caller passes). cut[r][sl] is the data offset where slice sl of
+ * run r begins, read from the record AT the boundary; every record read here
+ * passes host_entry_key's bounds test first. */
+static int slice_runs(const dbeel_run_view* runs, size_t n_runs,
+                      size_t big_run, uint64_t max_count, uint64_t S,
+                      std::vector<std::vector<uint64_t>>& bounds,
+                      std::vector<std::vector<uint64_t>>& cut) {
     std::vector<std::pair<const uint8_t*, uint64_t>> pivots; /* key,len */
     for (uint64_t j = 1; j < S; j++) {
         uint64_t klen;
@@ -7530,11 +7508,10 @@ extern "C" int dbeel_gpu_compact_sliced(const dbeel_run_view* runs,
         }
         pivots.push_back({k, klen});
     }
-    /* per run: slice boundary entry indices (first entry >= pivot) */
-    std::vector<std::vector<uint64_t>> bounds(n_runs);
     for (size_t r = 0; r < n_runs; r++) {
-        uint64_t n = runs[r].index_len / 16;
+        const uint64_t n = runs[r].index_len / 16;
         bounds[r].push_back(0);
+        cut[r].push_back(0);
         for (auto& pv : pivots) {
             uint64_t lo = bounds[r].back(), hi = n;
             while (lo < hi) {
@@ -7550,10 +7527,66 @@ extern "C" int dbeel_gpu_compact_sliced(const dbeel_run_view* runs,
                 else
                     hi = mid;
             }
+            uint64_t c = runs[r].data_len;
+            if (lo == 0) {
+                c = 0;
+            } else if (lo < n) {
+                uint64_t kl;
+                if (!host_entry_key(&runs[r], lo, &kl)) {
+                    set_err("corrupt index record in run %zu", r);
+                    return DBEEL_ERR_CORRUPT;
+                }
+                c = ld_u64_host(runs[r].index + lo * 16);
+            }
+            if (c < cut[r].back()) {
+                set_err("run %zu: index offsets not ascending", r);
+                return DBEEL_ERR_CORRUPT;
+            }
             bounds[r].push_back(lo);
+            cut[r].push_back(c);
         }
         bounds[r].push_back(n);
+        cut[r].push_back(runs[r].data_len);
     }
+    return DBEEL_OK;
+}
+
+extern "C" int dbeel_gpu_compact_sliced(const dbeel_run_view* runs,
+                                        size_t n_runs, int keep_tombstones,
+                                        int device,
+                                        uint64_t max_resident_bytes,
+                                        dbeel_compact_result* out) {
+    g_err[0] = 0;
+    if (!out) {
+        set_err("out is null");
+        return DBEEL_ERR_INVALID_ARG;
+    }
+    int rc = validate_runs(runs, n_runs);
+    if (rc) return rc;
+    rc = check_device_arg(device);
+    if (rc) return rc;
+    size_t big_run;
+    uint64_t max_count;
+    const uint64_t total_input =
+        input_extent(runs, n_runs, &big_run, &max_count);
+    uint64_t budget = max_resident_bytes;
+    if (!budget) {
+        HIP_CHECK(hipSetDevice(device));
+        size_t free_b = 0, total_b = 0;
+        HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+        /* input slab + output data + pfx/aux/cr/rrec intermediates stay
+         * under ~2.6x input for <= 64 runs; /3 leaves headroom */
+        budget = (uint64_t)(free_b / 3);
+    }
+    uint64_t S = budget ? (total_input + budget - 1) / budget : 1;
+    if (S <= 1 || max_count < 2 * S)
+        return dbeel_gpu_compact(runs, n_runs, keep_tombstones, device, out);
+
+    /* the slice views take their data offsets from the index records
+     * themselves (off_lo / off_hi below): cut is not needed here */
+    std::vector<std::vector<uint64_t>> bounds(n_runs), cut(n_runs);
+    rc = slice_runs(runs, n_runs, big_run, max_count, S, bounds, cut);
+    if (rc) return rc;
 
     memset(out, 0, sizeof *out);
     std::vector<uint8_t> acc_data, acc_index;
@@ -7699,16 +7732,10 @@ extern "C" int dbeel_gpu_compact_into(
     rc = validate_runs(runs, n_runs);
     if (rc) return rc;
 
-    uint64_t total_input = 0, max_count = 0;
-    size_t big_run = 0;
-    for (size_t r = 0; r < n_runs; r++) {
-        total_input += runs[r].data_len + runs[r].index_len;
-        uint64_t c = runs[r].index_len / 16;
-        if (c > max_count) {
-            max_count = c;
-            big_run = r;
-        }
-    }
+    size_t big_run;
+    uint64_t max_count;
+    const uint64_t total_input =
+        input_extent(runs, n_runs, &big_run, &max_count);
     uint64_t S = n_slices;
     if (!S) {
         uint64_t budget = max_resident_bytes;
@@ -7726,65 +7753,9 @@ extern "C" int dbeel_gpu_compact_into(
     if (S > max_count / 2) S = max_count / 2;
     if (S < 1) S = 1;
 
-    /* Slice boundaries, as compact_sliced finds them: pivots are evenly
-     * spaced keys of the largest run, bounds[r][sl] the first entry of run
-     * r not below pivot sl. cut[r][sl] is the data offset where slice sl
-     * of run r begins, read from the record AT the boundary; every record
-     * read here passes host_entry_key's bounds test first. */
     std::vector<std::vector<uint64_t>> bounds(n_runs), cut(n_runs);
-    {
-        std::vector<std::pair<const uint8_t*, uint64_t>> pivots;
-        for (uint64_t j = 1; j < S; j++) {
-            uint64_t klen;
-            const uint8_t* k =
-                host_entry_key(&runs[big_run], j * max_count / S, &klen);
-            if (!k) {
-                set_err("corrupt index record in run %zu", big_run);
-                return DBEEL_ERR_CORRUPT;
-            }
-            pivots.push_back({k, klen});
-        }
-        for (size_t r = 0; r < n_runs; r++) {
-            const uint64_t n = runs[r].index_len / 16;
-            bounds[r].push_back(0);
-            cut[r].push_back(0);
-            for (auto& pv : pivots) {
-                uint64_t lo = bounds[r].back(), hi = n;
-                while (lo < hi) {
-                    uint64_t mid = (lo + hi) >> 1;
-                    uint64_t kl;
-                    const uint8_t* k = host_entry_key(&runs[r], mid, &kl);
-                    if (!k) {
-                        set_err("corrupt index record in run %zu", r);
-                        return DBEEL_ERR_CORRUPT;
-                    }
-                    if (host_key_cmp(k, kl, pv.first, pv.second) < 0)
-                        lo = mid + 1;
-                    else
-                        hi = mid;
-                }
-                uint64_t c = runs[r].data_len;
-                if (lo == 0) {
-                    c = 0;
-                } else if (lo < n) {
-                    uint64_t kl;
-                    if (!host_entry_key(&runs[r], lo, &kl)) {
-                        set_err("corrupt index record in run %zu", r);
-                        return DBEEL_ERR_CORRUPT;
-                    }
-                    c = ld_u64_host(runs[r].index + lo * 16);
-                }
-                if (c < cut[r].back()) {
-                    set_err("run %zu: index offsets not ascending", r);
-                    return DBEEL_ERR_CORRUPT;
-                }
-                bounds[r].push_back(lo);
-                cut[r].push_back(c);
-            }
-            bounds[r].push_back(n);
-            cut[r].push_back(runs[r].data_len);
-        }
-    }
+    rc = slice_runs(runs, n_runs, big_run, max_count, S, bounds, cut);
+    if (rc) return rc;
 
     rc = select_device(device);
     if (rc) return rc;

@@ -24,6 +24,7 @@
 
 #include "../../include/dbeel_gpu.h"
 #include "../../include/dbeel_lsm.h"
+#include "engine_internal.h"
 
 namespace {
 
@@ -156,9 +157,6 @@ extern "C" int dbeel_bloom_contains(const uint8_t* bloom_bytes,
     *out = present;
     return DBEEL_OK;
 }
-
-/* defined in dbeel_gpu.hip (same library, not exported) */
-extern "C" void dbeel_set_last_error(const char* msg);
 
 extern "C" int dbeel_lsm_reader_open(const char* dir_c, int device,
                                      dbeel_gpu_reader** out,
@@ -618,12 +616,6 @@ extern "C" int dbeel_lsm_compact_tree(const char* dir_c,
 }
 
 /* ---- live reader over a directory (include/dbeel_lsm.h) ---- */
-
-/* defined in dbeel_gpu.hip (same library, not exported) */
-extern "C" uint64_t dbeel_reader_run_data_len(const dbeel_gpu_reader* rd,
-                                              size_t pos);
-
-extern "C" int dbeel_reader_drop_run(dbeel_gpu_reader* rd, size_t pos);
 
 namespace {
 /* Where a new sstable goes in a reader described by indices[0..*n): its

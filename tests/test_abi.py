@@ -180,3 +180,38 @@ def test_oracle_lib_exports():
     for sym in ("dbeel_oracle_compact", "dbeel_oracle_result_free",
                 "dbeel_oracle_last_error"):
         assert getattr(lib, sym, None) is not None, sym
+
+
+def test_compact_sliced_refuses_descending_offsets_on_the_host():
+    """The host slicer reads slice boundaries from the index records before
+    any kernel has validated them. A run whose records are all in bounds and
+    whose keys ascend, but whose entries lie in the data in reverse order,
+    has boundary offsets that descend: with max_resident_bytes set (so the
+    slice count comes from the argument, not the device) compact_sliced
+    refuses it as CORRUPT under the slicer's own text, before any device
+    call, so this needs no GPU."""
+    import struct
+
+    _built()
+    from dbeel_amd import engine
+    from dbeel_amd.format import Entry, build_run, encode_entry
+
+    big = build_run([Entry(b"k%02d" % i, b"v" * 8, i) for i in range(12)])
+    ents = [Entry(b"k%02d+" % i, b"w" * 8, 100 + i) for i in range(9)]
+    encs = [encode_entry(e) for e in ents]
+    # entry i is stored at the mirror position: offsets descend with i
+    offs, at = [0] * len(encs), 0
+    for i in reversed(range(len(encs))):
+        offs[i] = at
+        at += len(encs[i])
+    data = b"".join(reversed(encs))
+    index = b"".join(struct.pack("<QII", offs[i], 8 + len(e.key), len(encs[i]))
+                     for i, e in enumerate(ents))
+    runs = [big, (data, index)]
+    total = sum(len(d) + len(x) for d, x in runs)
+    budget = total // 3 + 1
+    assert (total + budget - 1) // budget == 3  # three slices, two pivots
+    with pytest.raises(engine.DbeelGpuError) as ei:
+        engine.compact_sliced(runs, True, device=0, max_resident_bytes=budget)
+    assert ei.value.code == 2  # DBEEL_ERR_CORRUPT
+    assert str(ei.value).endswith("run 1: index offsets not ascending")

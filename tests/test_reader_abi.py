@@ -140,3 +140,30 @@ def test_lsm_reader_open_refuses_more_than_64_sstables(tmp_path):
         lsm.open_reader(str(tmp_path), device=0)
     assert ei.value.code == 1  # INVALID_ARG
     assert "compact" in str(ei.value)
+
+
+def test_reader_get_key_batch_refusals_name_their_caller():
+    """A key batch whose offsets descend, or of 2^32 keys, is refused before
+    the reader handle is looked at or any device call is made: a zeroed
+    buffer stands in for the reader. The message is reader_get's own and
+    names the index; the result is left zeroed."""
+    import numpy as np
+
+    _built()
+    from dbeel_amd.engine import GetResult, _load_reader
+
+    lib = _load_reader()
+    u8p, u64p = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint64)
+    ka = np.frombuffer(b"abcdef", dtype=np.uint8)
+    koff = np.array([0, 4, 2, 6], dtype=np.uint64)  # descends at index 1
+    kp, op = ka.ctypes.data_as(u8p), koff.ctypes.data_as(u64p)
+    fake = (ctypes.c_uint8 * 8192)()
+    call = lib.dbeel_gpu_reader_get
+    for n, text in ((3, b"reader_get: key_offsets not ascending at 1"),
+                    (1 << 32, b"reader_get: 2^32 or more keys in one batch")):
+        res = GetResult()
+        res.n_keys = res.values_len = 9
+        assert call(fake, kp, op, n, ctypes.byref(res), None) == 1
+        assert lib.dbeel_gpu_last_error() == text
+        assert not bytes(res).strip(b"\0")
+    assert not bytes(fake).strip(b"\0")

@@ -112,6 +112,35 @@ def test_get_entries_null_arguments():
     assert not hits.view(np.uint8).any()
 
 
+def test_get_entries_key_batch_refusals_name_their_caller():
+    """A key batch whose offsets descend, or of 2^32 keys, is refused before
+    the reader handle is looked at or any device call is made: a zeroed
+    buffer stands in for the reader. The message is get_entries' own and
+    names the index; no caller buffer is touched."""
+    _built()
+    from dbeel_amd.engine import GetPage, _load_reader
+
+    lib = _load_reader()
+    kp, _, buf, keep = _args()
+    ka, _, hits, roff, rec = keep
+    koff = np.array([0, 2, 1, 4], dtype=np.uint64)  # descends at index 1
+    op = koff.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+    fake = (ctypes.c_uint8 * 8192)()
+    call = lib.dbeel_gpu_reader_get_entries
+    for n, text in (
+            (3, b"reader_get_entries: key_offsets not ascending at 1"),
+            (1 << 32, b"reader_get_entries: 2^32 or more keys in one batch")):
+        page = GetPage()
+        page.n_done = 9
+        assert call(fake, kp, op, n, ctypes.byref(buf), ctypes.byref(page),
+                    None) == INVALID_ARG
+        assert lib.dbeel_gpu_last_error() == text
+        assert page.n_done == 0
+    assert np.all(rec == 0xA5) and np.all(roff == 7)
+    assert not hits.view(np.uint8).any()
+    assert not bytes(fake).strip(b"\0")
+
+
 def test_compact_fetch_null_arguments():
     _built()
     from dbeel_amd.engine import _load_reader

@@ -131,6 +131,42 @@ def test_get_merged_null_arguments():
     assert not hits.view(np.uint8).any()
 
 
+def test_get_merged_key_batch_refusals_name_their_caller():
+    """A key batch whose offsets descend, or of 2^32 keys, is refused before
+    the reader handle is looked at or any device call is made: a zeroed
+    buffer stands in for the local reader and there are no sources. The
+    message is get_merged's own and names the index; no caller buffer is
+    touched."""
+    _built()
+    from dbeel_amd.engine import (MERGE_HIT_DTYPE, GetPage, MergeBuffers,
+                                  MergeHit, _load_reader)
+
+    lib = _load_reader()
+    u8p, u64p = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint64)
+    ka = np.frombuffer(b"abcd", dtype=np.uint8)
+    koff = np.array([0, 2, 1, 4], dtype=np.uint64)  # descends at index 1
+    hits = np.zeros(3, dtype=MERGE_HIT_DTYPE)
+    roff = np.full(4, 7, dtype=np.uint64)
+    rec = np.full(64, 0xA5, dtype=np.uint8)
+    buf = MergeBuffers(hits.ctypes.data_as(ctypes.POINTER(MergeHit)),
+                       roff.ctypes.data_as(u64p), rec.ctypes.data_as(u8p), 64)
+    kp, op = ka.ctypes.data_as(u8p), koff.ctypes.data_as(u64p)
+    fake = (ctypes.c_uint8 * 8192)()
+    call = lib.dbeel_gpu_reader_get_merged
+    for n, text in (
+            (3, b"reader_get_merged: key_offsets not ascending at 1"),
+            (1 << 32, b"reader_get_merged: 2^32 or more keys in one batch")):
+        page = GetPage()
+        page.n_done = 9
+        assert call(fake, kp, op, n, None, 0, ctypes.byref(buf),
+                    ctypes.byref(page), None) == INVALID_ARG
+        assert lib.dbeel_gpu_last_error() == text
+        assert page.n_done == 0
+    assert np.all(rec == 0xA5) and np.all(roff == 7)
+    assert not hits.view(np.uint8).any()
+    assert not bytes(fake).strip(b"\0")
+
+
 def test_model_self_check():
     mm.self_check()
 
