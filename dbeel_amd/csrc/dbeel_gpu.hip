@@ -16,23 +16,34 @@
  *                  run pair WITHIN a job, diagonal-partitioned
  *                  2048-position windows; blocks stage both prefix
  *                  segments into LDS coalesced and walk CORANK_STEPS
- *                  merged positions per thread (prefix-tied pairs are
- *                  settled ahead of the walk), recording crossranks
+ *                  merged positions per thread (a window's prefix-tied
+ *                  pairs are listed in LDS and settled by the whole
+ *                  block ahead of the walk), recording crossranks
  *                  (order = key bytes asc, timestamp i128 asc, run index
  *                  asc — lsm_tree.rs:52-71 + mod.rs:75-81) and
  *                  newest-wins supersession flags (lsm_tree.rs:1041-1044).
  *   k_rankreduce : crossranks -> job-local rank (+ job entry base);
  *                  winner/tombstone rules; strict-sortedness check
  *                  (flush invariant, lsm_tree.rs:925-946); one 16-B
- *                  rank-indexed record (keep flag in src bit 63).
- *   scans        : two rocPRIM exclusive scans (transform iterators,
- *                  plain u64/u32 + plus to stay on the decoupled-
- *                  lookback fast path) -> survivor byte offsets +
- *                  positions.
- *   k_emit       : output .index records (offset/key_size/full_size,
+ *                  rank-indexed record (keep flag in src bit 63); in the
+ *                  job path's packed mode also the packed (count, bytes)
+ *                  sum of every 2048-rank tile.
+ *   k_tilebase   : the tile sums -> exclusive tile bases (one block).
+ *   k_emit_tile  : one block per rank tile scans its tile from the base:
+ *                  output .index records (offset/key_size/full_size,
  *                  entry_writer.rs:79-87) + compacted source map + the
- *                  step totals record that winmap/copy read on-device.
- *   k_winmap/k_copy : verbatim survivor copy, balanced by DESTINATION
+ *                  step totals record that winmap/copy read on-device +
+ *                  the copy's window map where no survivor is larger
+ *                  than a window.
+ *   scans/k_emit : everywhere else (jobs past the packing bounds, reader,
+ *                  memtable, batch and scan paths): two rocPRIM
+ *                  exclusive scans (transform iterators, plain u64/u32 +
+ *                  plus to stay on the decoupled-lookback fast path) ->
+ *                  survivor byte offsets + positions, then k_emit;
+ *                  DBEEL_SCAN_MODE=rocprim: one packed scan +
+ *                  k_emit_packed on the job path, for A/B.
+ *   k_winmap/k_copy : (k_winmap only when emit did not fill the map)
+ *                  verbatim survivor copy, balanced by DESTINATION
  *                  granule (16-B granules per lane, window/grid geometry
  *                  picked per survivor size from interleaved A/Bs, LDS
  *                  granule->entry map) so throughput is independent of
@@ -97,6 +108,7 @@
 #include "engine_internal.h"
 
 #define MAX_RUNS 64
+#define JOB_ERR_WORDS 4 /* u32 words of a job's d_err ahead of the tile sums */
 
 static thread_local char g_err[512];
 
@@ -682,15 +694,16 @@ __global__ void k_prepare(RunsDesc R, uint64_t g0, uint64_t g1,
 #define CORANK_BLOCK 256
 #define CORANK_STEPS 8
 #define CORANK_BLOCK_POS (CORANK_BLOCK * CORANK_STEPS) /* 2048 */
-#ifndef CORANK_TIE_HINTS
-#define CORANK_TIE_HINTS 1 /* prefix-tied pairs settled ahead of the walk,
-                              per thread (k_corank scout). Each one holds
-                              two aux records in flight (24 VGPRs on the
-                              48-B tier); 1 keeps cfg3's kernel at 5
-                              waves/SIMD, 2 and 3 drop it to 4 and 3 and
-                              lose more on tie-free windows than they gain
-                               */
-#endif
+/* A window's tie list (k_corank): one u32 per prefix-tied pair, the staged
+ * slot x of run a in bits 0..10, the slot y of run b in bits 11..21, and,
+ * once the pair is settled, bit 22 valid, 23 keys equal, 24 a first. */
+#define TIE_XY_BITS 11
+#define TIE_XY_MASK ((1u << (2 * TIE_XY_BITS)) - 1)
+#define TIE_VALID (1u << 22)
+#define TIE_KEQ (1u << 23)
+#define TIE_AFIRST (1u << 24)
+static_assert(CORANK_BLOCK_POS <= (1 << TIE_XY_BITS),
+              "a staged slot must fit a tie-list field");
 #define CR_LOSER 0x80000000u
 #define CR_MASK 0x7FFFFFFFu
 
@@ -795,6 +808,17 @@ __global__ __launch_bounds__(BLK) void k_corank(
         /* per-thread sub-window: local diagonal search inside LDS */
         uint32_t L = lenA + lenB;
         uint32_t d = threadIdx.x * STEPS;
+        uint32_t ja = 0, jb = 0, dend = 0;
+        /* Scout: a prefix-only two-pointer sweep over the positions this
+         * thread walks notes every pair with equal prefixes. The sweep
+         * consumes both entries of such a pair, so a thread notes at most
+         * STEPS/2 of them and a window at most CORANK_BLOCK_POS/2. */
+        constexpr int MAXP = STEPS / 2;
+        uint32_t tie[MAXP]; /* noted pairs, then their settled entries */
+        uint32_t ntie = 0;
+        #pragma unroll
+        for (int m = 0; m < MAXP; m++)
+            tie[m] = TIE_XY_MASK; /* no pair: x + y < CORANK_BLOCK_POS */
         if (d < L) {
             uint32_t slo = d > lenB ? d - lenB : 0;
             uint32_t shi = d < lenA ? d : lenA;
@@ -805,74 +829,118 @@ __global__ __launch_bounds__(BLK) void k_corank(
                     return cmp_sfx_full<KB, TS>(R, aux, a, iaS + s, b,
                                                 ibS + u) < 0;
                 });
-            uint32_t ja = slo, jb = d - slo;
-            uint32_t dend = d + STEPS;
+            ja = slo, jb = d - slo;
+            dend = d + STEPS;
             if (dend > L) dend = L;
+            uint32_t x = ja, y = jb, c = d;
+            while (c < dend && x < lenA && y < lenB) {
+                uint64_t pa = sA[x], pb = sB[y];
+                if (pa < pb) {
+                    x++, c++;
+                } else if (pa > pb) {
+                    y++, c++;
+                } else {
+                    #pragma unroll
+                    for (int m = 0; m < MAXP; m++)
+                        if ((int)ntie == m) tie[m] = x | (y << TIE_XY_BITS);
+                    ntie++, x++, y++, c += 2;
+                }
+            }
+        }
 
-            /* Scout: a prefix-only two-pointer sweep over the staged
-             * entries this thread can reach notes the first M pairs with
-             * equal prefixes; their aux records are then fetched together
-             * and each pair is settled once, ahead of the walk, so the
-             * walk's serial steps do not each wait on a dependent global
-             * load. The notes are hints only: the walk looks a tied pair
-             * up here and settles it itself when it is not noted (more
-             * than M ties, prefix groups wider than 1x1, keys tied through
-             * the staged bytes), so ordering never depends on the sweep's
-             * provisional "consume both" rule. */
-            constexpr int M = CORANK_TIE_HINTS;
-            uint32_t hx[M], hy[M];
-            uint32_t hbits = 0; /* per hint m: bit 3m valid, 3m+1 keys
-                                   equal, 3m+2 a first */
+        /* The window's tie list, in ascending x: a block scan of the
+         * per-thread counts places each thread's pairs. The list lives in
+         * s_cr, which is free until the walk and holds twice the at most
+         * CORANK_BLOCK_POS/2 entries; the per-wave totals (<= 64 * MAXP
+         * each) take the two slack words of s_pfx, which nothing else
+         * touches. Every thread of the block takes part, with or without
+         * positions of its own. */
+        constexpr int NWAVE = BLK / 64;
+        static_assert(NWAVE * sizeof(uint16_t) <= 2 * sizeof(uint64_t) &&
+                          64 * MAXP <= 0xFFFF,
+                      "wave totals must fit the slack of s_pfx");
+        uint32_t* s_list = s_cr;
+        uint16_t* s_wtot = (uint16_t*)(s_pfx + CORANK_BLOCK_POS);
+        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+        uint32_t incl = ntie;
+        #pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            uint32_t up = __shfl_up(incl, o);
+            if (lane >= (uint32_t)o) incl += up;
+        }
+        if (lane == 63) s_wtot[wave] = incl;
+        __syncthreads();
+        uint32_t lbase = incl - ntie, n_list = 0;
+        #pragma unroll
+        for (int w = 0; w < NWAVE; w++) {
+            uint32_t wt = s_wtot[w];
+            if ((uint32_t)w < wave) lbase += wt;
+            n_list += wt;
+        }
+        /* n_list is the same in every thread: a window without prefix
+         * ties takes none of the barriers below */
+        if (n_list) {
             #pragma unroll
-            for (int m = 0; m < M; m++) hx[m] = hy[m] = ~0u;
-            {
-                uint32_t nh = 0, x = ja, y = jb, c = d;
-                while (c < dend && x < lenA && y < lenB && nh < M) {
-                    uint64_t pa = sA[x], pb = sB[y];
-                    if (pa < pb) {
-                        x++, c++;
-                    } else if (pa > pb) {
-                        y++, c++;
+            for (int m = 0; m < MAXP; m++)
+                if (m < (int)ntie) s_list[lbase + m] = tie[m];
+            __syncthreads();
+            /* Settle: the block's threads share the list evenly, whoever
+             * noted the pair. Consecutive entries index nearly consecutive
+             * aux records of both runs. Each pair is settled once, ahead
+             * of the walk, so the walk's serial steps do not each wait on
+             * a dependent global load. Keys tied through the staged bytes
+             * (deep) stay unsettled. */
+            const AuxT<KB, TS>* xa = aux + R.entry_base[a] + iaS;
+            const AuxT<KB, TS>* xb = aux + R.entry_base[b] + ibS;
+            for (uint32_t u = threadIdx.x; u < n_list; u += BLK) {
+                uint32_t e = s_list[u];
+                uint32_t hx = e & ((1u << TIE_XY_BITS) - 1);
+                uint32_t hy = (e >> TIE_XY_BITS) & ((1u << TIE_XY_BITS) - 1);
+                AuxT<KB, TS> ra = xa[hx], rb = xb[hy];
+                bool deep;
+                int k = cmp_keys_rec<KB, TS>(ra, rb, deep);
+                bool first = k < 0;
+                if (k == 0 && !deep) {
+                    if constexpr (TS) {
+                        first = ra.ts_hi != rb.ts_hi ? ra.ts_hi < rb.ts_hi
+                                : ra.ts_lo != rb.ts_lo
+                                    ? ra.ts_lo < rb.ts_lo
+                                    : a < b;
                     } else {
-                        #pragma unroll
-                        for (int m = 0; m < M; m++)
-                            if ((int)nh == m) hx[m] = x, hy[m] = y;
-                        nh++, x++, y++, c += 2;
+                        first = cmp_ts_run_blob(R, a, iaS + hx, b,
+                                                ibS + hy) < 0;
                     }
                 }
-                const AuxT<KB, TS>* xa = aux + R.entry_base[a] + iaS;
-                const AuxT<KB, TS>* xb = aux + R.entry_base[b] + ibS;
-                AuxT<KB, TS> ra[M], rb[M];
-                #pragma unroll
-                for (int m = 0; m < M; m++)
-                    if (m < (int)nh) {
-                        ra[m] = xa[hx[m]];
-                        rb[m] = xb[hy[m]];
-                    }
-                #pragma unroll
-                for (int m = 0; m < M; m++)
-                    if (m < (int)nh) {
-                        bool deep;
-                        int k = cmp_keys_rec<KB, TS>(ra[m], rb[m], deep);
-                        bool first = k < 0;
-                        if (k == 0 && !deep) {
-                            if constexpr (TS) {
-                                first = ra[m].ts_hi != rb[m].ts_hi
-                                            ? ra[m].ts_hi < rb[m].ts_hi
-                                        : ra[m].ts_lo != rb[m].ts_lo
-                                            ? ra[m].ts_lo < rb[m].ts_lo
-                                            : a < b;
-                            } else {
-                                first = cmp_ts_run_blob(R, a, iaS + hx[m], b,
-                                                        ibS + hy[m]) < 0;
-                            }
-                        }
-                        if (!deep)
-                            hbits |= (1u | (k == 0 ? 2u : 0u) |
-                                      (first ? 4u : 0u)) << (3 * m);
-                    }
+                if (!deep)
+                    s_list[u] = e | TIE_VALID | (k == 0 ? TIE_KEQ : 0u) |
+                                (first ? TIE_AFIRST : 0u);
             }
+            __syncthreads();
+            /* Each thread takes its own entries back into registers and
+             * clears their slots, and only then may any walk store to
+             * s_cr. On sorted runs the walks overwrite every staged slot
+             * exactly once, so nothing of the list could reach the
+             * write-back anyway. On a flagged input (an unsorted run, a
+             * corrupt entry's zero prefix) the threads' splits need not
+             * fit together and a slot can stay unwritten: it then holds
+             * zero, a crossrank that is in range like every other, and
+             * not a list entry, whose flag bits would make a rank far
+             * past the job's last. */
+            #pragma unroll
+            for (int m = 0; m < MAXP; m++)
+                if (m < (int)ntie) {
+                    tie[m] = s_list[lbase + m];
+                    s_list[lbase + m] = 0;
+                }
+            __syncthreads();
+        }
 
+        /* The settled entries are hints only: the walk looks a tied pair
+         * up among its thread's entries and settles it itself when it is
+         * not there (a pair the sweep's provisional "consume both" rule
+         * mis-paired, prefix groups wider than 1x1, deep keys), so
+         * ordering never depends on the list. */
+        if (d < L) {
             for (uint32_t pos = d; pos < dend; pos++) {
                 bool take_a;
                 bool both = false; /* this step compared (ja, jb) */
@@ -888,13 +956,13 @@ __global__ __launch_bounds__(BLK) void k_corank(
                         take_a = pa < pb;
                     } else {
                         uint32_t h = 0;
+                        const uint32_t xy = ja | (jb << TIE_XY_BITS);
                         #pragma unroll
-                        for (int m = 0; m < M; m++)
-                            if (hx[m] == ja && hy[m] == jb)
-                                h = hbits >> (3 * m);
-                        if (h & 1u) {
-                            keq = h & 2u;
-                            take_a = h & 4u;
+                        for (int m = 0; m < MAXP; m++)
+                            if ((tie[m] & TIE_XY_MASK) == xy) h = tie[m];
+                        if (h & TIE_VALID) {
+                            keq = h & TIE_KEQ;
+                            take_a = h & TIE_AFIRST;
                         } else {
                             take_a = tie_eval<KB, TS>(R, aux, a, iaS + ja, b,
                                                       ibS + jb, keq);
@@ -969,54 +1037,111 @@ static_assert(sizeof(RankRec) == 16, "rank record must be 16B");
 #define RR_KEEP (1ull << 63)
 #define RR_OFF_MASK 0xFFFFFFFFFFFFull
 
+/* The packed survivor sums: bytes in the low 38 bits, count in the high 26
+ * (see RankRecPacked below for the bounds that keep them apart). */
+#define PK_SHIFT 38
+#define PK_MASK ((1ull << PK_SHIFT) - 1)
+
+/* Rank tiles of the survivor-offset stage (further down). */
+#define EMIT_BLOCK 256
+#define EMIT_ITEMS 8
+#define EMIT_TILE (EMIT_BLOCK * EMIT_ITEMS) /* 2048 ranks */
+
+/* Adds each lane's (tile, value) into tile_sum with one atomic per stretch
+ * of consecutive lanes that share a tile, never 64 lanes on one address.
+ * The lanes of a wave hold consecutive entries of one run (of two at a run
+ * seam), whose ranks rise with the lane, so a wave has a handful of
+ * stretches. Stretches are told apart by position, not by tile alone, so
+ * a tile that comes back after a seam is simply added to twice. Every lane
+ * of the wave must call this; lanes without an entry pass v = 0. */
+__device__ __forceinline__ void tile_sum_add(uint64_t* tile_sum,
+                                             uint64_t tile, uint64_t v) {
+    const uint32_t lane = threadIdx.x & 63u;
+    uint64_t prev = __shfl_up(tile, 1);
+    uint64_t heads = __ballot(lane == 0 || prev != tile);
+    /* the stretch of this lane ends before the next head above it */
+    uint64_t above = lane == 63 ? 0ull : heads & ~((2ull << lane) - 1);
+    uint32_t end =
+        above ? (uint32_t)__ffsll((unsigned long long)above) - 1 : 64u;
+    #pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        uint64_t dn = __shfl_down(v, o);
+        if (lane + o < end) v += dn;
+    }
+    if (((heads >> lane) & 1) && v)
+        atomicAdd((unsigned long long*)(tile_sum + tile),
+                  (unsigned long long)v);
+}
+
 /* Reduce per-pair crossranks to the global rank, apply the winner /
  * tombstone rules, and emit the rank-indexed scratch records. Also checks
  * each run is strictly sorted by key (flush invariant,
- * lsm_tree.rs:925-946) on the dense pfx/aux arrays. */
+ * lsm_tree.rs:925-946) on the dense pfx/aux arrays. With tile_sum set,
+ * every kept entry's packed (count, bytes) contribution is added to the
+ * sum of its rank tile, for the tile-wise survivor offsets. The loop is
+ * block-uniform, because the wave reduction inside needs every lane. */
 template <int KB, bool TS>
 __global__ void k_rankreduce(RunsDesc R, const uint64_t* pfx,
                              const AuxT<KB, TS>* aux, const uint32_t* cr,
                              RankRec* rrec, int keep_tombstones,
-                             uint32_t* err) {
+                             uint32_t* err, uint64_t* tile_sum) {
     uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-         g < R.total; g += stride) {
-        int r = run_of(R, g);
-        uint64_t i = g - R.entry_base[r];
+    for (uint64_t gb = (uint64_t)blockIdx.x * blockDim.x; gb < R.total;
+         gb += stride) {
+        uint64_t g = gb + threadIdx.x;
+        uint64_t tile = ~0ull, contrib = 0;
+        int r = 0;
+        uint64_t i = 0;
         EView e;
-        if (!load_entry(R, r, i, e)) {
-            /* k_prepare has flagged this input; keep memory safe and park
-             * the entry at its local slot (results will be discarded) */
-            RankRec z = {0, 8, 32};
-            rrec[g] = z;
-            continue;
+        bool ok = false;
+        if (g < R.total) {
+            r = run_of(R, g);
+            i = g - R.entry_base[r];
+            ok = load_entry(R, r, i, e);
+            if (!ok) {
+                /* k_prepare has flagged this input; keep memory safe and
+                 * park the entry at its local slot (results will be
+                 * discarded) */
+                RankRec z = {0, 8, 32};
+                rrec[g] = z;
+            }
         }
-        if (i + 1 < R.count[r]) {
-            uint64_t p0 = pfx[g], p1 = pfx[g + 1];
-            if (p0 > p1 ||
-                (p0 == p1 &&
-                 cmp_keys_sfx<KB, TS>(R, aux, r, i, r, i + 1) >= 0))
-                atomicOr(err, DERR_UNSORTED);
-        }
+        if (ok) {
+            if (i + 1 < R.count[r]) {
+                uint64_t p0 = pfx[g], p1 = pfx[g + 1];
+                if (p0 > p1 ||
+                    (p0 == p1 &&
+                     cmp_keys_sfx<KB, TS>(R, aux, r, i, r, i + 1) >= 0))
+                    atomicOr(err, DERR_UNSORTED);
+            }
 
-        /* rank is local to the entry's JOB (independent jobs share one
-         * launch); the job's entry base turns it into the global rrec
-         * slot, so job outputs concatenate in job order */
-        uint64_t rank = i + R.entry_base[R.job_lo[r]];
-        bool winner = true;
-        int nslots = (int)R.job_hi[r] - (int)R.job_lo[r] - 1;
-        for (int s = 0; s < nslots; s++) {
-            uint32_t v = cr[(uint64_t)s * R.total + g];
-            rank += v & CR_MASK;
-            winner &= !(v & CR_LOSER);
+            /* rank is local to the entry's JOB (independent jobs share one
+             * launch); the job's entry base turns it into the global rrec
+             * slot, so job outputs concatenate in job order */
+            uint64_t rank = i + R.entry_base[R.job_lo[r]];
+            bool winner = true;
+            int nslots = (int)R.job_hi[r] - (int)R.job_lo[r] - 1;
+            for (int s = 0; s < nslots; s++) {
+                uint32_t v = cr[(uint64_t)s * R.total + g];
+                rank += v & CR_MASK;
+                winner &= !(v & CR_LOSER);
+            }
+            uint64_t dlen = (uint64_t)e.full_size - 32 - e.klen;
+            bool keep = winner && (keep_tombstones || dlen != 0);
+            RankRec m;
+            m.src = ((uint64_t)r << 48) | e.off | (keep ? RR_KEEP : 0);
+            m.key_size = e.key_size;
+            m.full_size = e.full_size;
+            /* rank < total on every valid input; crossranks of a flagged
+             * one (results discarded) are not trusted with an address */
+            if (rank < R.total) {
+                rrec[rank] = m;
+                tile = rank / EMIT_TILE;
+                if (keep)
+                    contrib = (uint64_t)e.full_size | (1ull << PK_SHIFT);
+            }
         }
-        uint64_t dlen = (uint64_t)e.full_size - 32 - e.klen;
-        bool keep = winner && (keep_tombstones || dlen != 0);
-        RankRec m;
-        m.src = ((uint64_t)r << 48) | e.off | (keep ? RR_KEEP : 0);
-        m.key_size = e.key_size;
-        m.full_size = e.full_size;
-        rrec[rank] = m;
+        if (tile_sum) tile_sum_add(tile_sum, tile, contrib);
     }
 }
 
@@ -1029,8 +1154,6 @@ __global__ void k_rankreduce(RunsDesc R, const uint64_t* pfx,
  * (sums stay in-field, so lane-wise u64 addition never carries across);
  * that halves the scan's passes over rrec. Larger jobs fall back to two
  * scans. */
-#define PK_SHIFT 38
-#define PK_MASK ((1ull << PK_SHIFT) - 1)
 struct RankRecSize {
     __device__ uint64_t operator()(const RankRec& r) const {
         return (r.src & RR_KEEP) ? (uint64_t)r.full_size : 0ull;
@@ -1145,6 +1268,179 @@ __global__ void k_emit_packed(RunsDesc R, const RankRec* rrec,
     }
 }
 
+/* ------------------------------------------------------------------ */
+/* Survivor offsets by rank tile (packed mode of the job path)         */
+/*                                                                     */
+/* A tile is EMIT_TILE consecutive ranks. k_rankreduce, which knows    */
+/* every entry's keep flag and size when it writes the rank record,    */
+/* adds the entry's packed contribution (RankRecPacked) to its tile's  */
+/* sum; k_tilebase turns the few thousand sums into exclusive bases;   */
+/* k_emit_tile scans its own tile from that base and writes what       */
+/* k_emit_packed writes. The rank records are read once, and no        */
+/* per-entry offset array exists. Sums of packed values stay in-field  */
+/* for the reason given above RankRecPacked, in any order of addition. */
+/* ------------------------------------------------------------------ */
+__device__ __forceinline__ uint64_t packed_contrib(const RankRec& r) {
+    return RankRecPacked{}(r);
+}
+
+/* s_v slot of tile-local rank i: one pad word per EMIT_ITEMS, so that
+ * both the rank-per-lane and the EMIT_ITEMS-per-lane access patterns
+ * spread over the LDS banks */
+__device__ __forceinline__ uint32_t emit_slot(uint32_t i) {
+    return i + i / EMIT_ITEMS;
+}
+
+/* Exclusive scan of the tile sums, in place: one block, 1024 sums per
+ * round, the running total carried from round to round. No block waits
+ * for another. */
+#define TILEBASE_BLOCK 1024
+__global__ __launch_bounds__(TILEBASE_BLOCK) void k_tilebase(
+    uint64_t* tile_sum, uint32_t n_tiles) {
+    __shared__ uint64_t s_w[TILEBASE_BLOCK / 64];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint64_t carry = 0;
+    for (uint32_t t0 = 0; t0 < n_tiles; t0 += TILEBASE_BLOCK) {
+        uint32_t t = t0 + threadIdx.x;
+        uint64_t v = t < n_tiles ? tile_sum[t] : 0ull;
+        uint64_t incl = v;
+        #pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            uint64_t up = __shfl_up(incl, o);
+            if (lane >= (uint32_t)o) incl += up;
+        }
+        if (lane == 63) s_w[wave] = incl;
+        __syncthreads();
+        uint64_t before = 0, all = 0;
+        #pragma unroll
+        for (int w = 0; w < TILEBASE_BLOCK / 64; w++) {
+            uint64_t wt = s_w[w];
+            if ((uint32_t)w < wave) before += wt;
+            all += wt;
+        }
+        if (t < n_tiles) tile_sum[t] = carry + before + incl - v;
+        carry += all;
+        __syncthreads();
+    }
+}
+
+/* One block per tile. The tile's rank records are loaded coalesced (item k
+ * of thread t is rank k * EMIT_BLOCK + t of the tile); their packed
+ * contributions go through LDS so that each thread scans EMIT_ITEMS
+ * consecutive ranks, and come back as exclusive (position, offset) values
+ * for the records the threads still hold. Writes what k_emit_packed
+ * writes. With win_shift != 0 (copy windows of 1 << win_shift bytes,
+ * win_cap slots in win_p0) it also fills the copy's window map: the
+ * survivor whose bytes cover a window start is the window's first one, and
+ * a survivor no larger than a window covers at most one start. A larger
+ * one sets *need_winmap instead, and k_winmap fills the map as before. */
+__global__ __launch_bounds__(EMIT_BLOCK) void k_emit_tile(
+    RunsDesc R, const RankRec* rrec, const uint64_t* tile_base,
+    uint64_t total, uint8_t* out_index, uint64_t* src_map,
+    const uint32_t* err, StepTotals* tot, uint32_t win_shift,
+    uint64_t win_cap, uint32_t* win_p0, uint32_t* need_winmap) {
+    __shared__ uint64_t s_v[EMIT_TILE + EMIT_TILE / EMIT_ITEMS];
+    __shared__ uint64_t s_w[EMIT_BLOCK / 64];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t n_tiles = (total + EMIT_TILE - 1) / EMIT_TILE;
+    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint64_t g0 = tile * EMIT_TILE;
+        uint64_t src[EMIT_ITEMS];
+        uint32_t ksz[EMIT_ITEMS], fsz[EMIT_ITEMS];
+        #pragma unroll
+        for (int k = 0; k < EMIT_ITEMS; k++) {
+            uint64_t g = g0 + (uint32_t)k * EMIT_BLOCK + threadIdx.x;
+            src[k] = 0, ksz[k] = 0, fsz[k] = 0;
+            if (g < total) {
+                RankRec m = rrec[g];
+                src[k] = m.src, ksz[k] = m.key_size, fsz[k] = m.full_size;
+            }
+            s_v[emit_slot(k * EMIT_BLOCK + threadIdx.x)] =
+                (src[k] & RR_KEEP) ? ((uint64_t)fsz[k] | (1ull << PK_SHIFT))
+                                   : 0ull;
+        }
+        __syncthreads();
+        uint64_t loc[EMIT_ITEMS], sum = 0;
+        #pragma unroll
+        for (int k = 0; k < EMIT_ITEMS; k++) {
+            loc[k] = sum; /* exclusive within the thread */
+            sum += s_v[emit_slot(threadIdx.x * EMIT_ITEMS + k)];
+        }
+        uint64_t incl = sum;
+        #pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            uint64_t up = __shfl_up(incl, o);
+            if (lane >= (uint32_t)o) incl += up;
+        }
+        if (lane == 63) s_w[wave] = incl;
+        __syncthreads();
+        uint64_t base = tile_base[tile] + incl - sum;
+        #pragma unroll
+        for (int w = 0; w < EMIT_BLOCK / 64; w++)
+            if ((uint32_t)w < wave) base += s_w[w];
+        /* a thread rewrites only the slots it has just read */
+        #pragma unroll
+        for (int k = 0; k < EMIT_ITEMS; k++)
+            s_v[emit_slot(threadIdx.x * EMIT_ITEMS + k)] = base + loc[k];
+        __syncthreads();
+        #pragma unroll
+        for (int k = 0; k < EMIT_ITEMS; k++) {
+            uint64_t g = g0 + (uint32_t)k * EMIT_BLOCK + threadIdx.x;
+            if (g >= total) continue;
+            uint64_t v = s_v[emit_slot(k * EMIT_BLOCK + threadIdx.x)];
+            uint64_t p = v >> PK_SHIFT, off = v & PK_MASK;
+            const uint32_t key_size = ksz[k], full_size = fsz[k];
+            if (g + 1 == total) {
+                RankRec last = {src[k], key_size, full_size};
+                store_totals(tot, err, last, off, p);
+            }
+            /* p < total always holds on valid input; on a flagged one
+             * (totals zero, nothing copied) the sizes may not add up */
+            if (!(src[k] & RR_KEEP) || p >= total) continue;
+            uint8_t* rec = out_index + p * 16;
+            __builtin_memcpy(rec, &off, 8);
+            __builtin_memcpy(rec + 8, &key_size, 4);
+            __builtin_memcpy(rec + 12, &full_size, 4);
+            src_map[p] = (uint64_t)(R.data[(src[k] >> 48) & 0x7FFF] +
+                                    (src[k] & RR_OFF_MASK));
+            if (win_shift) {
+                if (full_size <= (1u << win_shift)) {
+                    /* the first window start at or after off */
+                    uint64_t w = (off + (1u << win_shift) - 1) >> win_shift;
+                    if ((w << win_shift) < off + full_size && w < win_cap)
+                        win_p0[w] = (uint32_t)p;
+                } else {
+                    *need_winmap = 1;
+                }
+            }
+        }
+        __syncthreads(); /* s_v and s_w are reused by the next tile */
+    }
+}
+
+/* The packed scan value at rank g (exclusive), rebuilt from the tile bases
+ * where no per-entry array holds it: one block sums the contributions of
+ * the ranks of g's tile below g. Used for the few job boundaries a batched
+ * job's result is sliced at, after the step. */
+__global__ __launch_bounds__(EMIT_BLOCK) void k_tile_value_at(
+    const RankRec* rrec, const uint64_t* tile_base, uint64_t g,
+    uint64_t* out) {
+    __shared__ uint64_t s_w[EMIT_BLOCK / 64];
+    const uint64_t g0 = g / EMIT_TILE * EMIT_TILE;
+    uint64_t v = 0;
+    for (uint64_t i = g0 + threadIdx.x; i < g; i += EMIT_BLOCK)
+        v += packed_contrib(rrec[i]);
+    #pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+    if ((threadIdx.x & 63u) == 0) s_w[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t s = tile_base[g / EMIT_TILE];
+        for (int w = 0; w < EMIT_BLOCK / 64; w++) s += s_w[w];
+        *out = s;
+    }
+}
+
 /* Balanced verbatim copy: a 16-KiB destination window per 256-thread
  * block, 4 x 16-B granules per thread (independent loads/stores for ILP;
  * granule passes are thread-contiguous so stores coalesce). Entries are
@@ -1161,9 +1457,12 @@ __global__ void k_emit_packed(RunsDesc R, const RankRec* rrec,
  * 2 = 512 x 16 KiB, 3 = 512 x 32 KiB */
 
 /* Per destination window, the largest survivor p with offset(p) <= window
- * start — one thread per window (parallel), consumed by k_copy. */
+ * start — one thread per window (parallel), consumed by k_copy. With
+ * `need` set and clear, the map is already there and nothing runs. */
 __global__ void k_winmap(const uint8_t* out_index, const StepTotals* tot,
-                         uint32_t win, uint32_t* win_p0) {
+                         uint32_t win, uint32_t* win_p0,
+                         const uint32_t* need) {
+    if (need && !*need) return;
     const uint64_t n_surv = tot->n_surv, total_bytes = tot->total_out;
     uint64_t n_windows = (total_bytes + win - 1) / win;
     uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
@@ -1602,7 +1901,14 @@ struct dbeel_gpu_job {
     uint8_t* d_outdata = nullptr;
     void* d_scantmp = nullptr;
     size_t scantmp_bytes = 0;
-    uint32_t* d_err = nullptr;
+    uint32_t* d_err = nullptr;   /* one allocation, zeroed per step: the
+                                    error words (2 x u32), the flag that
+                                    asks for k_winmap (u32, + pad), then
+                                    the rank-tile sums                  */
+    uint32_t* d_needwin = nullptr; /* = d_err + 2                       */
+    uint64_t* d_tilesum = nullptr; /* = d_err + 4: n_tiles packed sums,
+                                      exclusive bases after k_tilebase  */
+    uint32_t n_tiles = 0;
     uint64_t* d_pfx = nullptr;   /* dense big-endian key prefixes       */
     void* d_aux = nullptr;       /* dense 64B search records            */
     uint32_t* d_cr = nullptr;    /* per-pair crossranks, column-major   */
@@ -1618,7 +1924,10 @@ struct dbeel_gpu_job {
     uint64_t input_bytes = 0;
     std::vector<uint64_t> job_gbase; /* entry base per job (+ total) */
     /* last-run results */
-    int last_scan_packed = 0; /* d_dstoff holds packed (pos<<38|off) */
+    int last_scan_packed = 0; /* 1: d_dstoff holds packed (pos<<38|off);
+                                 2: tile mode, no per-entry array: the
+                                 same packed value is rebuilt on demand
+                                 from d_tilesum and d_rank */
     uint64_t out_data_len = 0;
     uint64_t out_entries = 0;
     bool have_result = false;
@@ -1742,7 +2051,11 @@ static int job_create_impl(const dbeel_run_view* runs, size_t n_runs,
     HIP_CHECK(hipMalloc(&job->d_outindex, n * 16));
     HIP_CHECK(hipMalloc(&job->d_srcmap, n * sizeof(uint64_t)));
     HIP_CHECK(hipMalloc(&job->d_outdata, total_data ? total_data : 16));
-    HIP_CHECK(hipMalloc(&job->d_err, 2 * sizeof(uint32_t)));
+    job->n_tiles = (uint32_t)((n + EMIT_TILE - 1) / EMIT_TILE);
+    HIP_CHECK(hipMalloc(&job->d_err, JOB_ERR_WORDS * sizeof(uint32_t) +
+                                         job->n_tiles * sizeof(uint64_t)));
+    job->d_needwin = job->d_err + 2;
+    job->d_tilesum = (uint64_t*)(job->d_err + JOB_ERR_WORDS);
     HIP_CHECK(hipMalloc(&job->d_pfx, n * sizeof(uint64_t)));
     HIP_CHECK(hipMalloc(&job->d_tot, sizeof(StepTotals)));
     HIP_CHECK(hipHostMalloc(&job->h_tot, sizeof(StepTotals)));
@@ -1914,6 +2227,18 @@ extern "C" int dbeel_gpu_job_fetch_job(dbeel_gpu_job* job, size_t job_idx,
     uint32_t pos0 = 0, pos1 = (uint32_t)job->out_entries;
     hipStream_t s = job->stream;
     int pk = job->last_scan_packed;
+    if (pk == 2) {
+        /* tile mode kept no per-entry values: rebuild the two asked for,
+         * into the slots the rocPRIM scan would have left them in */
+        if (g0 > 0)
+            hipLaunchKernelGGL(k_tile_value_at, dim3(1), dim3(EMIT_BLOCK),
+                               0, s, job->d_rank, job->d_tilesum, g0,
+                               job->d_dstoff + g0);
+        if (g1 < job->total_entries)
+            hipLaunchKernelGGL(k_tile_value_at, dim3(1), dim3(EMIT_BLOCK),
+                               0, s, job->d_rank, job->d_tilesum, g1,
+                               job->d_dstoff + g1);
+    }
     if (g0 > 0) {
         HIP_CHECK(hipMemcpyAsync(&off0, job->d_dstoff + g0, 8,
                                  hipMemcpyDeviceToHost, s));
@@ -2241,10 +2566,14 @@ extern "C" uint32_t dbeel_gpu_grid_for(uint64_t work_items, uint32_t block) {
  * or superseded entries shift the average across a class boundary (say
  * 60% dropped tombstones among 1 KiB values: 470 B in, 1088 B out); every
  * variant is correct for every size, the choice is a speed matter only. */
-static void launch_copy(hipStream_t s, const uint8_t* out_index,
-                        const uint64_t* src_map, uint32_t* win_p0,
-                        const StepTotals* tot, uint64_t in_entries,
-                        uint64_t in_bytes, uint8_t* out_data) {
+struct CopyGeom {
+    int variant;
+    uint32_t win, blk;
+    uint64_t gcap;
+    uint64_t windows; /* upper bound, from the input bytes */
+};
+
+static CopyGeom copy_geometry(uint64_t in_entries, uint64_t in_bytes) {
     int variant = -1;
     if (const char* v = getenv("DBEEL_COPY_VARIANT")) variant = atoi(v);
     uint64_t gcap = 0;
@@ -2271,11 +2600,25 @@ static void launch_copy(hipStream_t s, const uint8_t* out_index,
                    : (variant == 4) ? 65536
                                     : 16384;
     uint32_t blk = (variant >= 2) ? 512 : 256;
-    uint64_t windows = (in_bytes + win - 1) / win; /* upper bound */
+    /* every window size is a power of two: k_emit_tile shifts by it */
+    return CopyGeom{variant, win, blk, gcap, (in_bytes + win - 1) / win};
+}
+
+/* need_winmap: null, or a device flag that is clear when the emit kernel
+ * has filled win_p0 itself (k_emit_tile); k_winmap then returns at once. */
+static void launch_copy(hipStream_t s, const uint8_t* out_index,
+                        const uint64_t* src_map, uint32_t* win_p0,
+                        const StepTotals* tot, uint64_t in_entries,
+                        uint64_t in_bytes, uint8_t* out_data,
+                        const uint32_t* need_winmap = nullptr) {
+    const CopyGeom G = copy_geometry(in_entries, in_bytes);
+    const int variant = G.variant;
+    const uint32_t win = G.win, blk = G.blk;
+    const uint64_t windows = G.windows, gcap = G.gcap;
     if (!windows) return;
     uint32_t grid = windows > gcap ? (uint32_t)gcap : (uint32_t)windows;
     hipLaunchKernelGGL(k_winmap, dim3(pick_grid(windows, 256)), dim3(256),
-                       0, s, out_index, tot, win, win_p0);
+                       0, s, out_index, tot, win, win_p0, need_winmap);
     void (*kc)(const uint8_t*, const uint64_t*, const uint32_t*,
                const StepTotals*, uint8_t*) = k_copy<256, 16384>;
     if (variant == 1) kc = k_copy<256, 8192>;
@@ -2301,7 +2644,23 @@ extern "C" int dbeel_gpu_job_run(dbeel_gpu_job* job, int keep_tombstones,
     job->have_result = false;
 
     int skip_prep = job->prep_valid;
-    HIP_CHECK(hipMemsetAsync(job->d_err, 0, 2 * sizeof(uint32_t), s));
+    /* How the survivor offsets are made. Packed (one u64 carries bytes and
+     * count) where the job fits its bounds; there by rank tile unless
+     * DBEEL_SCAN_MODE=rocprim asks for the per-entry rocPRIM scan, for
+     * A/B. DBEEL_SCAN_MODE=two forces the two-scan form of larger jobs. */
+    bool packed = n < (1ull << 26) &&
+                  job->total_data_bytes < (1ull << PK_SHIFT);
+    bool tiled = packed;
+    if (const char* m = getenv("DBEEL_SCAN_MODE")) {
+        if (!strcmp(m, "two")) packed = tiled = false;
+        if (!strcmp(m, "rocprim")) tiled = false;
+    }
+    HIP_CHECK(hipMemsetAsync(
+        job->d_err, 0,
+        tiled ? JOB_ERR_WORDS * sizeof(uint32_t) +
+                    job->n_tiles * sizeof(uint64_t)
+              : 2 * sizeof(uint32_t),
+        s));
 
     HIP_CHECK(hipEventRecord(job->ev[0], s));
     if (n && !skip_prep) launch_prepare(job, 0, n, s);
@@ -2310,6 +2669,10 @@ extern "C" int dbeel_gpu_job_run(dbeel_gpu_job* job, int keep_tombstones,
         uint32_t grid = pick_grid(n, 256);
         uint64_t cgrid = job->total_chunks;
         if (cgrid > 16384) cgrid = 16384;
+        if (const char* g = getenv("DBEEL_CORANK_GRID")) {
+            long v = atol(g); /* fewer blocks: several windows per block */
+            if (v >= 1 && (uint64_t)v < cgrid) cgrid = (uint64_t)v;
+        }
         int corank_wide = 0; /* A/B: 512-thread corank blocks */
         if (const char* w = getenv("DBEEL_CORANK_BLOCK"))
             corank_wide = atoi(w) >= 512;
@@ -2341,18 +2704,18 @@ extern "C" int dbeel_gpu_job_run(dbeel_gpu_job* job, int keep_tombstones,
             }
             hipLaunchKernelGGL((k_rankreduce<KB, TS>), dim3(grid), dim3(256),
                                0, s, job->desc, job->d_pfx, aux, job->d_cr,
-                               job->d_rank, keep_tombstones, job->d_err);
+                               job->d_rank, keep_tombstones, job->d_err,
+                               tiled ? job->d_tilesum : nullptr);
         });
     }
     HIP_CHECK(hipEventRecord(job->ev[1], s));
-    bool packed = n < (1ull << 26) &&
-                  job->total_data_bytes < (1ull << PK_SHIFT);
-    if (const char* m = getenv("DBEEL_SCAN_MODE")) {
-        if (!strcmp(m, "two")) packed = false;
-    }
+    const CopyGeom geom = copy_geometry(n, job->total_data_bytes);
     if (n) {
         size_t tmp = job->scantmp_bytes;
-        if (packed)
+        if (tiled)
+            hipLaunchKernelGGL(k_tilebase, dim3(1), dim3(TILEBASE_BLOCK), 0,
+                               s, job->d_tilesum, job->n_tiles);
+        else if (packed)
             HIP_CHECK(rocprim::exclusive_scan(
                 job->d_scantmp, tmp,
                 rocprim::make_transform_iterator(job->d_rank,
@@ -2366,7 +2729,15 @@ extern "C" int dbeel_gpu_job_run(dbeel_gpu_job* job, int keep_tombstones,
     HIP_CHECK(hipEventRecord(job->ev[2], s));
     if (n) {
         uint32_t grid = pick_grid(n, 256);
-        if (packed)
+        if (tiled)
+            hipLaunchKernelGGL(k_emit_tile, dim3(job->n_tiles),
+                               dim3(EMIT_BLOCK), 0, s, job->desc,
+                               job->d_rank, job->d_tilesum, n,
+                               job->d_outindex, job->d_srcmap, job->d_err,
+                               job->d_tot,
+                               (uint32_t)__builtin_ctz(geom.win),
+                               geom.windows, job->d_winp0, job->d_needwin);
+        else if (packed)
             hipLaunchKernelGGL(k_emit_packed, dim3(grid), dim3(256), 0, s,
                                job->desc, job->d_rank, job->d_dstoff, n,
                                job->d_outindex, job->d_srcmap, job->d_err,
@@ -2386,7 +2757,8 @@ extern "C" int dbeel_gpu_job_run(dbeel_gpu_job* job, int keep_tombstones,
     HIP_CHECK(hipEventRecord(job->ev[4], s));
     if (n)
         launch_copy(s, job->d_outindex, job->d_srcmap, job->d_winp0,
-                    job->d_tot, n, job->total_data_bytes, job->d_outdata);
+                    job->d_tot, n, job->total_data_bytes, job->d_outdata,
+                    tiled ? job->d_needwin : nullptr);
     HIP_CHECK(hipEventRecord(job->ev[5], s));
     HIP_CHECK(hipMemcpyAsync(job->h_tot, job->d_tot, sizeof(StepTotals),
                              hipMemcpyDeviceToHost, s));
@@ -2400,7 +2772,7 @@ extern "C" int dbeel_gpu_job_run(dbeel_gpu_job* job, int keep_tombstones,
                     : "corrupt entry/index record");
         return DBEEL_ERR_CORRUPT;
     }
-    job->last_scan_packed = packed ? 1 : 0;
+    job->last_scan_packed = tiled ? 2 : packed ? 1 : 0;
     uint64_t total_out = job->h_tot->total_out;
     uint64_t n_surv = job->h_tot->n_surv;
 
